@@ -10,6 +10,14 @@ Synthetic data (random token ids of the target shape), random-init weights.
 Timing: W untimed warmup steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize() on both sides; MAX step time over ranks;
 rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print the
+line. ``--dump-outputs DIR`` additionally writes what the last timed step
+computed (see dump_outputs) so two builds can be compared output for
+output; seeds are fixed, so the same arguments give the same inputs.
+``--full`` is where measurements beyond the headline figure belong (extra
+precisions, baselines, per-kernel passes); there are none today, so it runs
+the same path.
 """
 import argparse
 import json
@@ -47,7 +55,17 @@ def parse_args():
     p.add_argument("--gc-cnt", type=int, default=None,
                    help="checkpoint only the first N layers (288 GB HBM3E "
                         "rarely needs all of them)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "outputs to DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements a plain run skips "
+                        "(none today: the plain run is already only the "
+                        "headline figure)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
 
 
 def build_model(args, cfg):
@@ -74,6 +92,58 @@ def build_model(args, cfg):
         mcfg = llama_tiny(cp_mode=cp_mode)
     torch.manual_seed(1234)
     return LlamaForCausalLM(mcfg), mcfg
+
+
+# per-tensor sample size for --dump-outputs: FSDP flattens each wrapped layer
+# into one parameter, so Llama-2-7B yields 33 tensors -> 0.5 MB of float32;
+# even 70B unwrapped (723 tensors, 12 MB) stays far under the 64 MB cap
+_DUMP_SAMPLE = 4096
+_DUMP_CAP_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, loss, model):
+    """Write what a caller of the timed step receives, as float32 .npy:
+
+    - ``loss.npy``: the loss the last timed step returned, shape (1,);
+    - ``params_sample.npy``: the parameters that step left behind (the
+      step's other result), sampled at fixed seeded positions — up to
+      ``_DUMP_SAMPLE`` elements of each tensor, concatenated in
+      ``named_parameters()`` order;
+    - ``params_sample_index.json``: name, numel and slice of each tensor in
+      the sample.
+
+    Positions depend only on the tensor's order and size, so two builds run
+    with the same arguments sample the same elements.
+
+    Called on rank 0 only and reads ``named_parameters()`` of the
+    accelerated model as they are: with more than one rank under FSDP or TP
+    that is rank 0's local shard (and rank 0's loss), not the gathered
+    parameters. With ``--gpus 1`` it is the whole model.
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    chunks, index, off = [], [], 0
+    gen = torch.Generator(device="cpu")
+    for i, (name, p) in enumerate(model.named_parameters()):
+        flat = p.detach().reshape(-1)
+        n = flat.numel()
+        if n == 0:
+            continue
+        if n > _DUMP_SAMPLE:
+            gen.manual_seed(9000 + i)
+            pos = torch.randint(0, n, (_DUMP_SAMPLE,), generator=gen)
+            flat = flat[pos.sort().values.to(flat.device)]
+        chunks.append(flat.float().cpu())
+        index.append({"name": name, "numel": n, "start": off,
+                      "stop": off + flat.numel()})
+        off += flat.numel()
+    sample = torch.cat(chunks).numpy()
+    assert sample.nbytes + 4 <= _DUMP_CAP_BYTES, sample.nbytes
+    np.save(os.path.join(out_dir, "params_sample.npy"), sample)
+    with open(os.path.join(out_dir, "params_sample_index.json"), "w") as f:
+        json.dump(index, f, indent=1)
 
 
 def main():
@@ -195,6 +265,9 @@ def main():
     else:
         tokens_per_step = bs * local_seq * world
     toks_per_s = tokens_per_step * args.steps / secs
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)
 
     if rank == 0:
         out = {
