@@ -104,6 +104,52 @@ DEVINLINE attn_u32x2 attn_tr16_pair(unsigned a0, unsigned a1,
   return lo;
 }
 
+// Dual-use LDS image of a [rows][D x 16-bit] tile: one copy that is
+// conflict-free for the 32x32x16 A-operand row reads (ds_read_b128, lane =
+// row) AND for the B-operand transposed reads (ds_read_b64_tr_b16). The tile
+// is cut into 8-row x 32-column subtiles of 512 B; inside a subtile a row is
+// 64 B and its four 16-byte chunks are XORed with (row>>2)&3. attn_dual_off
+// is the byte offset of 16-byte chunk ch (0..D/8-1) of row `row`.
+// Bank rule, bank = (addr/4) % 64 (256 B wrap):
+//   row read, 16-lane group = rows 16n..16n+15 at one ch: 64*(row&3) picks
+//     one of 4 64-byte quarters, the (row>>2)&3 XOR one of its 4 chunks ->
+//     16 distinct chunks of the 256 B;
+//   transposed read, 32-lane half = 4 rows (row&3 = 0..3) x 4 chunks x 2
+//     8-byte halves -> 256 contiguous bytes mod 256.
+template <int D>
+DEVINLINE unsigned attn_dual_off(int row, int ch) {
+  return (unsigned)((row >> 3) * (16 * D) + (ch >> 2) * 512 +
+                    (row & 7) * 64 + (((ch & 3) ^ ((row >> 2) & 3)) << 4));
+}
+
+// Staging order for the dual-use image: chunk index c -> (row, ch) such that
+// 16 consecutive c cover 4 rows x 4 chunks of one subtile, i.e. 256
+// contiguous LDS bytes mod 256 (a row-major order would put the 4 subtiles
+// of one row on the same banks, 4-way on the ds_write_b128). The global side
+// still reads whole 64-byte pieces of 4 rows per 16 lanes.
+template <int D>
+DEVINLINE void attn_dual_stage_coord(int c, int& row, int& ch) {
+  constexpr int SC = D / 32;
+  const int g = c >> 4;
+  row = (g / SC) * 4 + ((c >> 2) & 3);
+  ch = (g % SC) * 4 + (c & 3);
+}
+
+// Per-lane byte offsets for the transposed reads of the 32x32x16 B operand
+// X[k = r0 + 8*hi + j][col = 32*a + (lane&31)] (r0 a multiple of 16) from a
+// dual-use image: lane 4q+p of a 16-lane group points at row q, elements
+// 4p..4p+3 of the group's 16 columns. b0 serves k-slots j = 0..3, b1 serves
+// j = 4..7; the XOR makes the two differ by more than a constant, hence two
+// bases. Add (r0/8)*16*D + a*512 as an immediate.
+template <int D>
+DEVINLINE void attn_dual_tr_bases(int lane, unsigned& b0, unsigned& b1) {
+  const int hi = lane >> 5, g1 = (lane >> 4) & 1;
+  const int q = (lane & 15) >> 2, p = lane & 3;
+  const int ch = 2 * g1 + (p >> 1);
+  b0 = attn_dual_off<D>(hi * 8 + q, ch) + 8 * (p & 1);
+  b1 = attn_dual_off<D>(hi * 8 + 4 + q, ch) + 8 * (p & 1);
+}
+
 // counter-based dropout RNG (splitmix64): deterministic keep-decision per
 // (seed, flat attention index) — the backward kernels regenerate the same
 // mask the forward applied (reference: FA2 philox rng_state).

@@ -1,16 +1,41 @@
 // Flash-attention v2 BACKWARD for gfx950 (CDNA4 MFMA).
 //
 // Three kernels (recompute variant — deterministic, no atomics):
-//   1. fa_bwd_preprocess: delta[b,h,sq] = rowsum(dO * O)
+//   1. fa_bwd_preprocess: delta[b,h,sq] = rowsum(dO * O), 16-byte loads.
 //   2. fa_bwd_dkv: grid over 128-key tiles (4-wave WG, wave = 32 keys);
-//      K/V fragments live in registers; per 64-row Q tile (Q, dO, lse,
-//      delta staged in LDS) it recomputes P from (S, stored lse), computes
-//      dP, dS, and accumulates dV += P^T dO and dK += dS^T Q, using the
-//      cvt_pk + permlane32_swap fragment redistribution (T12) to turn the
-//      QK^T accumulator layout into mfma A-operands.
-//   3. fa_bwd_dq: forward structure (8-wave WG, wave = 32 q rows); K
-//      natural + K^T + V natural staged in LDS per 64-key tile; dQ += dS K
-//      accumulated in registers.
+//      K fragments live in registers, V in LDS; per 32-row Q tile (Q, dO,
+//      lse, delta staged in LDS) it recomputes P from (S, stored lse),
+//      computes dP, dS, and accumulates dV += P^T dO and dK += dS^T Q, using
+//      the cvt_pk + permlane32_swap fragment redistribution (T12) to turn
+//      the QK^T accumulator layout into mfma A-operands.
+//   3. fa_bwd_dq: forward structure (8-wave WG, wave = 32 q rows); K and V
+//      staged in LDS per 128-key tile; dQ += dS K accumulated in registers.
+//
+// LDS images. Every tile (Q, dO, V in dkv; K, V in dq) is stored ONCE, in
+// the dual-use image of attn_common.h (attn_dual_off): 8-row x 32-column
+// subtiles of 512 B with the 16-byte chunks of a row XORed by (row>>2)&3.
+// The same copy serves the row reads (ds_read_b128, A operand of S and dP)
+// and the transposed reads (ds_read_b64_tr_b16, B operand of dK, dV and dQ),
+// both conflict-free; the staging writes go in attn_dual_stage_coord order,
+// also conflict-free. There is no transposed K copy.
+//
+// Buffer rotation. Both kernels keep TWO staging buffers and one barrier per
+// tile. Iteration i computes from buffer i&1 and fills buffer (i+1)&1 with
+// tile i+1:
+//   dkv: at the top of the iteration (load + LDS write, then compute); the
+//        sweep over (head, q tile) is flattened so this runs across heads.
+//        Holding the tile in registers across the MFMA phases spills at
+//        D=128 (256 VGPRs, two workgroups per CU), so the overlap comes from
+//        the other waves and the second workgroup, which no longer meet a
+//        barrier between staging and compute.
+//   dq:  per 64-key half: global loads issued before the half's MFMAs, LDS
+//        write after them (16 VGPRs in flight).
+// The barrier that ends iteration i does both jobs: it publishes buffer
+// (i+1)&1 for iteration i+1, and it retires every wave's reads of buffer i&1
+// before iteration i+1 overwrites it. The writes of iteration i need no
+// barrier of their own: buffer (i+1)&1 was last read in iteration i-1, whose
+// closing barrier every wave has passed. The prologue barrier publishes
+// buffer 0 (and the V image in dkv).
 //
 // P is normalized against the stored global lse and delta comes from the
 // global (out, dout), so the same kernels serve per-block ring-attention
@@ -30,26 +55,43 @@
 // ---------------------------------------------------------------------------
 // 1. preprocess: delta = rowsum(dO * O)   [b,h,sq] fp32
 // ---------------------------------------------------------------------------
-template <bool FP16>
+// One 16-byte chunk of dO and of O per lane: D/8 lanes share a row and a
+// wave takes 64/(D/8) rows. Lane m of a row holds the pair products
+// p[4m..4m+3] (pair k = elements 2k, 2k+1); the shuffles below add them in
+// the order of a 64-lane xor butterfly over k (offsets 32..1, absent pairs
+// being exact zeros), so delta keeps the rounding of a pair-per-lane sum.
+template <bool FP16, int D>
 __global__ void fa_bwd_preprocess_kernel(const short* __restrict__ dO,
                                          const short* __restrict__ O,
                                          float* __restrict__ delta, int b,
-                                         int sq, int hq, int D) {
-  const long row = (long)blockIdx.x * (blockDim.x / WAVE) +
-                   (threadIdx.x / WAVE);
+                                         int sq, int hq) {
+  constexpr int LPR = D / 8;          // lanes per row
+  constexpr int RPW = WAVE / LPR;     // rows per wave
   const int lane = threadIdx.x % WAVE;
+  const int m = lane % LPR;
+  const long row = ((long)blockIdx.x * (blockDim.x / WAVE) +
+                    (threadIdx.x / WAVE)) * RPW + lane / LPR;
   const long rows = (long)b * sq * hq;
-  if (row >= rows) return;
-  const short* dr = dO + row * D;
-  const short* orow = O + row * D;
-  float acc = 0.f;
-  for (int i = lane * 2; i < D; i += WAVE * 2) {
-    acc += AttnElem<FP16>::to_f32(dr[i]) * AttnElem<FP16>::to_f32(orow[i]) +
-           AttnElem<FP16>::to_f32(dr[i + 1]) *
-               AttnElem<FP16>::to_f32(orow[i + 1]);
+  s16x8 d8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  s16x8 o8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (row < rows) {
+    d8 = *reinterpret_cast<const s16x8*>(dO + row * D + m * 8);
+    o8 = *reinterpret_cast<const s16x8*>(O + row * D + m * 8);
   }
-  acc = wave_reduce_sum(acc);
-  if (lane == 0) {
+  float p[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    p[i] = AttnElem<FP16>::to_f32(d8[2 * i]) *
+               AttnElem<FP16>::to_f32(o8[2 * i]) +
+           AttnElem<FP16>::to_f32(d8[2 * i + 1]) *
+               AttnElem<FP16>::to_f32(o8[2 * i + 1]);
+#pragma unroll
+  for (int off = LPR / 2; off > 0; off >>= 1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) p[i] += __shfl_xor(p[i], off, 64);
+  }
+  const float acc = (p[0] + p[2]) + (p[1] + p[3]);
+  if (m == 0 && row < rows) {
     const int h = row % hq;
     const long bs = row / hq;
     const long bb = bs / sq, s = bs % sq;
@@ -76,19 +118,16 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
   constexpr int NA = D / 32;
   constexpr int QT = 32;            // q rows per staged tile
   constexpr int KVWG = 128;         // keys per workgroup (4 waves x 32)
-  // transposed tiles [D][32]: 64B rows with a ((d>>3)&3)<<4 byte-XOR —
-  // staging lanes differ in d by multiples of 8, so the XOR must use bits
-  // >=3 of d to spread write banks; reads (b128, 16-lane groups over
-  // d = a*32+col) become conflict-free since (d&3, (d>>3)&3) is distinct
-  // per lane
-  constexpr int TS = 32;
+  constexpr int TILE_B = QT * D * 2;        // bytes of one Q (or dO) image
+  constexpr int BUF_B = 2 * TILE_B;         // one buffer = Q image + dO image
+  constexpr int CPT = QT * D / 8 / 256;     // 16-byte chunks per thread
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  short* q_lds = reinterpret_cast<short*>(smem);            // [QT][D] swz
-  short* do_lds = q_lds + QT * D;                           // [QT][D] swz
-  short* v_lds = do_lds + QT * D;                           // [KVWG][D] swz
-  float* lse_lds = reinterpret_cast<float*>(v_lds + KVWG * D);
-  float* del_lds = lse_lds + QT;
+  // [2 buffers][Q image, dO image], dual-use image (attn_common.h)
+  char* qd_lds = smem;
+  short* v_lds = reinterpret_cast<short*>(smem + 2 * BUF_B);  // [KVWG][D], same image
+  float* st_lds = reinterpret_cast<float*>(v_lds + KVWG * D);
+  // st_lds: [2 buffers][lse[QT], delta[QT]]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -112,6 +151,64 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
     if (q_lens != nullptr) qlimit = min(qlimit, q_lens[b]);
   }
 
+  int q_lo = 0;
+  if (CAUSAL) q_lo = max(0, kv0wg - shift);
+  int q_hi = qlimit;
+  if (HAS_WINDOW && wl >= 0)
+    q_hi = min(q_hi, kv0wg + KVWG - 1 - shift + wl + 1);
+  const int qt0 = q_lo / QT;
+  const int qt1 = (max(q_hi, 0) + QT - 1) / QT;
+  // the (head, q tile) sweep, heads outer, flattened so the prefetch runs
+  // across the head boundary
+  const int n_tiles = qt1 > qt0 ? gqa * (qt1 - qt0) : 0;
+
+  // ---- staging of one Q/dO/lse/delta tile, split into a global-load half
+  // (into registers) and an LDS-write half ---------------------------------
+  s16x8 pq[CPT], pd[CPT];
+  float pst = 0.f;
+  auto tile_load = [&](int h, int q0) {
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      int row, ch;
+      attn_dual_stage_coord<D>(tid + i * 256, row, ch);
+      const int qrow = q0 + row;
+      pq[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      pd[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (qrow < sq) {
+        const long src = ((long)(b * sq + qrow) * hq + h) * D + ch * 8;
+        pq[i] = *reinterpret_cast<const s16x8*>(Q + src);
+        pd[i] = *reinterpret_cast<const s16x8*>(dOut + src);
+      }
+    }
+    if (tid < 2 * QT) {
+      // threads 0..QT-1 fetch lse, QT..2QT-1 fetch delta
+      const int qrow = q0 + (tid & (QT - 1));
+      const long idx = ((long)b * hq + h) * sq + min(qrow, sq - 1);
+      const float oob = tid < QT ? INFINITY : 0.f;
+      pst = (qrow < sq) ? (tid < QT ? LSE[idx] : DELTA[idx]) : oob;
+    }
+  };
+  auto tile_store = [&](int buf) {
+    char* dst = qd_lds + buf * BUF_B;
+    // the offsets are recomputed per tile from an opaque copy of tid: kept
+    // as loop invariants they would cost registers the MFMA phases need
+    int t_ = tid;
+    asm volatile("" : "+v"(t_));
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      int row, ch;
+      attn_dual_stage_coord<D>(t_ + i * 256, row, ch);
+      const unsigned off = attn_dual_off<D>(row, ch);
+      *reinterpret_cast<s16x8*>(dst + off) = pq[i];
+      *reinterpret_cast<s16x8*>(dst + TILE_B + off) = pd[i];
+    }
+    if (tid < 2 * QT) st_lds[buf * 2 * QT + tid] = pst;
+  };
+
+  // loader position: (head, q tile) of the next tile to fetch
+  int ld_gh = 0, ld_qt = qt0;
+  if (n_tiles > 0) tile_load(kh * gqa, qt0 * QT);
+
   // K fragments in registers; V staged once in LDS for the whole workgroup
   bf16x8 kfrag[NT];
   {
@@ -131,27 +228,33 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
     constexpr int CHUNKS = KVWG * D / 8;
     const long vbase = ((long)b * sk * hk + kh) * D;
     for (int c = tid; c < CHUNKS; c += 256) {
-      const int row = c / (D / 8);
-      const int d0 = (c % (D / 8)) * 8;
+      int row, ch;
+      attn_dual_stage_coord<D>(c, row, ch);
       const int key = kv0wg + row;
       s16x8 vv8 = {0, 0, 0, 0, 0, 0, 0, 0};
       if (key < sk)
         vv8 = *reinterpret_cast<const s16x8*>(V + vbase +
-                                              (long)key * hk * D + d0);
-      unsigned byte = row * (D * 2) + d0 * 2;
-      byte ^= (unsigned)((row & 7) << 4);
-      *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(v_lds) + byte) = vv8;
+                                              (long)key * hk * D + ch * 8);
+      *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(v_lds) +
+                                attn_dual_off<D>(row, ch)) = vv8;
     }
-    __syncthreads();
   }
+  if (n_tiles > 0) tile_store(0);
+  __syncthreads();   // V image and buffer 0 visible
 
-  // per-lane constant address for the ds_read_b64_tr_b16 B-frag reads
-  // (see the DKV_TR_STEP comment below)
-  const int m4 = (lane & 15) >> 2;
-  const int dl0 = ((lane >> 4) & 1) * 16 + (lane & 3) * 4;
-  const unsigned tr_addr = (unsigned)(size_t)q_lds +
-      (unsigned)((hi * 8 + m4) * (D * 2)) +
-      (((unsigned)(dl0 * 2)) ^ ((unsigned)(m4 << 4)));
+  // per-lane constant offsets into a Q image: row reads (A operand, row =
+  // col, chunk 2t+hi: even t at row_off, odd t at row_off^32, +512 per two
+  // t). The two transposed-read addresses (attn_dual_tr_bases) are
+  // loop-carried and hop between the two buffers, one register each: the
+  // budget is 256 VGPRs with none spare.
+  const unsigned row_off = attn_dual_off<D>(col, hi);
+  unsigned tr0, tr1;
+  attn_dual_tr_bases<D>(lane, tr0, tr1);
+  tr0 += (unsigned)(size_t)qd_lds;
+  tr1 += (unsigned)(size_t)qd_lds;
+  // this wave's 32 keys of the V image (same row/chunk offsets as Q)
+  const char* vwave =
+      reinterpret_cast<const char*>(v_lds) + wid * 4 * (16 * D);
 
   f32x16 dkacc[NA], dvacc[NA];
 #pragma unroll
@@ -160,74 +263,48 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
     dvacc[a] = f32x16(0.f);
   }
 
-  int q_lo = 0;
-  if (CAUSAL) q_lo = max(0, kv0wg - shift);
-  int q_hi = qlimit;
-  if (HAS_WINDOW && wl >= 0)
-    q_hi = min(q_hi, kv0wg + KVWG - 1 - shift + wl + 1);
-  const int qt0 = q_lo / QT;
-  const int qt1 = (max(q_hi, 0) + QT - 1) / QT;
+  int c_qt = qt0;
+  for (int it = 0; it < n_tiles; ++it) {
+    const int cur = it & 1;
+    const int q0 = c_qt * QT;
+    const bool has_next = it + 1 < n_tiles;   // workgroup-uniform
+    // ---- stage the next tile into the OTHER buffer before computing this
+    // one. Every wave left that buffer's reads behind at the barrier that
+    // ended the previous iteration, so no barrier is needed here, and a wave
+    // waiting for its loads does not hold up the waves (and the second
+    // resident workgroup) that are already in their MFMA phases. The staging
+    // registers are dead before the MFMA phases, which have no VGPR to spare
+    // (holding the tile in registers across them spills at D=128). ---------
+    if (has_next) {
+      if (++ld_qt == qt1) { ld_qt = qt0; ++ld_gh; }
+      tile_load(kh * gqa + ld_gh, ld_qt * QT);
+      tile_store(cur ^ 1);
+    }
 
-  for (int gh = 0; gh < gqa; ++gh) {
-    const int h = kh * gqa + gh;
-    for (int qt = qt0; qt < qt1; ++qt) {
-      const int q0 = qt * QT;
-      // ---- cooperative staging: natural (swizzled) + transposed tiles ----
-      {
-        constexpr int CHUNKS = QT * D / 8;
-        for (int c = tid; c < CHUNKS; c += 256) {
-          const int row = c / (D / 8);
-          const int d0 = (c % (D / 8)) * 8;
-          const int qrow = q0 + row;
-          s16x8 qv = {0, 0, 0, 0, 0, 0, 0, 0};
-          s16x8 dv8 = {0, 0, 0, 0, 0, 0, 0, 0};
-          if (qrow < sq) {
-            const long src = ((long)(b * sq + qrow) * hq + h) * D + d0;
-            qv = *reinterpret_cast<const s16x8*>(Q + src);
-            dv8 = *reinterpret_cast<const s16x8*>(dOut + src);
-          }
-          unsigned byte = row * (D * 2) + d0 * 2;
-          byte ^= (unsigned)((row & 7) << 4);
-          *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(q_lds) + byte) =
-              qv;
-          *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(do_lds) + byte) =
-              dv8;
-        }
-        for (int r = tid; r < QT; r += 256) {
-          const int qrow = q0 + r;
-          const long idx = ((long)b * hq + h) * sq + min(qrow, sq - 1);
-          lse_lds[r] = (qrow < sq) ? LSE[idx] : INFINITY;
-          del_lds[r] = (qrow < sq) ? DELTA[idx] : 0.f;
-        }
-      }
-      __syncthreads();
+    const char* qcur = qd_lds + cur * BUF_B;
+    const float* lse_lds = st_lds + cur * 2 * QT;
+    const float* del_lds = lse_lds + QT;
 
-      // per-wave skip: this wave's keys [key_b, key_b+31] have no valid q
-      // in the tile (causal diagonal / window-left bound) — staging and
-      // barriers are cooperative, so only the compute is guarded
-      bool wave_active = true;
-      if (CAUSAL && q0 + QT - 1 < key_b - shift) wave_active = false;
-      if (HAS_WINDOW && wl >= 0 && q0 > key_b + 31 - shift + wl)
-        wave_active = false;
+    // per-wave skip: this wave's keys [key_b, key_b+31] have no valid q
+    // in the tile (causal diagonal / window-left bound) — staging and
+    // barriers are cooperative, so only the compute is guarded. The branch
+    // is wave-uniform: EXEC is all ones at the transposed reads inside.
+    bool wave_active = true;
+    if (CAUSAL && q0 + QT - 1 < key_b - shift) wave_active = false;
+    if (HAS_WINDOW && wl >= 0 && q0 > key_b + 31 - shift + wl)
+      wave_active = false;
 
-      if (wave_active) {
+    if (wave_active) {
       // S = Q K^T and dP = dO V^T, both D[q=CROW][key=col]
       f32x16 s = f32x16(0.f);
       f32x16 dp = f32x16(0.f);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        const int row = col;
-        unsigned byte = row * (D * 2) + (t * 16 + hi * 8) * 2;
-        byte ^= (unsigned)((row & 7) << 4);
-        bf16x8 qf = *reinterpret_cast<const bf16x8*>(
-            reinterpret_cast<const char*>(q_lds) + byte);
-        bf16x8 df = *reinterpret_cast<const bf16x8*>(
-            reinterpret_cast<const char*>(do_lds) + byte);
-        const int vrow = wid * 32 + col;
-        unsigned vbyte = vrow * (D * 2) + (t * 16 + hi * 8) * 2;
-        vbyte ^= (unsigned)((vrow & 7) << 4);
-        bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-            reinterpret_cast<const char*>(v_lds) + vbyte);
+        const unsigned byte =
+            ((t & 1) ? (row_off ^ 32u) : row_off) + (t >> 1) * 512;
+        bf16x8 qf = *reinterpret_cast<const bf16x8*>(qcur + byte);
+        bf16x8 df = *reinterpret_cast<const bf16x8*>(qcur + TILE_B + byte);
+        bf16x8 vf = *reinterpret_cast<const bf16x8*>(vwave + byte);
         s = AttnElem<FP16>::mfma(qf, kfrag[t], s);
         dp = AttnElem<FP16>::mfma(df, vf, dp);
       }
@@ -250,30 +327,26 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
       }
       // A-frags over the q k-dim; step tp covers q rows 16tp..16tp+15.
       // B-frags X[q = 16tp + hi*8 + jj][d = a*32 + col] come straight from
-      // the NATURAL swizzled q/do images via ds_read_b64_tr_b16 (probe:
-      // csrc/tools/tr16_probe.hip; see attn_common.h). With the
-      // (row&7)<<4 swizzle the byte address decomposes ADDITIVELY:
-      //   byte = (hi*8+m4)*D*2 + [dl0*2 ^ (m4<<4)]      (per-lane const)
-      //        + tp*16*D*2 + r*4*D*2 + ((a^r))*64       (compile-time)
-      // so all 4*NA reads share ONE address VGPR + offset: immediates —
-      // no per-iteration address registers to hoist.
+      // the dual-use q/do images via ds_read_b64_tr_b16 (probe:
+      // csrc/tools/tr16_probe.hip; see attn_common.h). The byte address is
+      //   tr0 (jj = 0..3) or tr1 (jj = 4..7)            (per-lane)
+      //   + tp*32*D + a*512 (+ TILE_B for dO)           (compile-time)
+      // so all 4*NA reads of a tile use two address VGPRs + offset:
+      // immediates.
 
 #define DKV_TR_STEP(tp_, a_)                                               \
       {                                                                    \
         attn_u32x2 ql_, qh_, dl_, dh_;                                     \
         asm volatile(                                                      \
-            "ds_read_b64_tr_b16 %0, %4 offset:%c5\n\t"                   \
-            "ds_read_b64_tr_b16 %1, %4 offset:%c6\n\t"                   \
+            "ds_read_b64_tr_b16 %0, %4 offset:%c6\n\t"                   \
+            "ds_read_b64_tr_b16 %1, %5 offset:%c6\n\t"                   \
             "ds_read_b64_tr_b16 %2, %4 offset:%c7\n\t"                   \
-            "ds_read_b64_tr_b16 %3, %4 offset:%c8\n\t"                   \
+            "ds_read_b64_tr_b16 %3, %5 offset:%c7\n\t"                   \
             "s_waitcnt lgkmcnt(0)"                                         \
             : "=v"(ql_), "=v"(qh_), "=v"(dl_), "=v"(dh_)                   \
-            : "v"(tr_addr),                                                \
-              "i"((tp_) * 16 * D * 2 + (a_) * 64),                         \
-              "i"((tp_) * 16 * D * 2 + 4 * D * 2 + ((a_) ^ 1) * 64),       \
-              "i"(QT * D * 2 + (tp_) * 16 * D * 2 + (a_) * 64),            \
-              "i"(QT * D * 2 + (tp_) * 16 * D * 2 + 4 * D * 2 +            \
-                  ((a_) ^ 1) * 64));                                       \
+            : "v"(tr0), "v"(tr1),                                          \
+              "i"((tp_) * 32 * D + (a_) * 512),                            \
+              "i"(TILE_B + (tp_) * 32 * D + (a_) * 512));                  \
         attn_u32x4 uq_ = {ql_.x, ql_.y, qh_.x, qh_.y};                     \
         attn_u32x4 ud_ = {dl_.x, dl_.y, dh_.x, dh_.y};                     \
         bf16x8 qbf = __builtin_bit_cast(bf16x8, uq_);                      \
@@ -306,9 +379,15 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
         }
       }
 #undef DKV_TR_STEP
-      }  // wave_active
-      __syncthreads();
-    }
+    }  // wave_active
+
+    // one barrier per tile: it publishes buffer cur^1 and retires this
+    // iteration's reads of buffer cur before the next iteration writes it
+    __syncthreads();
+    if (++c_qt == qt1) c_qt = qt0;
+    const unsigned hop = cur ? (unsigned)-BUF_B : (unsigned)BUF_B;
+    tr0 += hop;
+    tr1 += hop;
   }
 
   // ---- epilogue: D[key = key_b + CROW(r,hi)][d = a*32 + col] ------------
@@ -344,15 +423,18 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
                       const int* __restrict__ k_lens) {
   constexpr int NT = D / 16;
   constexpr int NA = D / 32;
-  // 128-key staged tiles: one 8-wave WG is resident anyway (VGPR-bound),
-  // so the bigger LDS footprint (96 KB at D=128) costs no occupancy and
-  // halves the barrier + staging-iteration count.
+  // 128-key staged tiles, two buffers of (K image + V image): one 8-wave WG
+  // is resident anyway (VGPR-bound), so 128 KB of LDS at D=128 costs no
+  // occupancy. The tile is computed, and the next one prefetched, in two
+  // 64-key halves so the in-flight registers stay at 4 x 16 B per thread.
   constexpr int KVB = 128;
+  constexpr int TILE_B = KVB * D * 2;       // bytes of one K (or V) image
+  constexpr int BUF_B = 2 * TILE_B;
+  constexpr int HALF_B = TILE_B / 2;        // 64 rows of a dual-use image
+  constexpr int CPT = 64 * D / 8 / 512;     // chunks per thread per half
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  short* k_lds = reinterpret_cast<short*>(smem);     // [128][D] swz
-  short* kt_lds = k_lds + KVB * D;                   // [D][128] swz
-  short* v_lds = kt_lds + D * KVB;                   // [128][D] swz
+  // [2 buffers][K image, V image], both in the dual-use image
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -375,6 +457,51 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
     if (k_lens != nullptr) klimit = min(klimit, k_lens[b]);
     if (q_lens != nullptr) qlimit = min(qlimit, q_lens[b]);
   }
+
+  int kv_hi_key = klimit;
+  if (CAUSAL) kv_hi_key = min(kv_hi_key, q0wg + 255 + shift + 1);
+  int kv_lo_key = 0;
+  if (HAS_WINDOW && wl >= 0) kv_lo_key = max(0, q0wg + shift - wl);
+  const int t0 = kv_lo_key / KVB;
+  const int t1 = (max(kv_hi_key, 0) + KVB - 1) / KVB;
+  const long kbase = ((long)b * sk * hk + kh) * D;
+
+  // ---- staging of one 64-key half of a K/V tile: global-load half (into
+  // registers) and LDS-write half ------------------------------------------
+  s16x8 pk[CPT], pv[CPT];
+  int srow[CPT];
+  unsigned soff[CPT];
+#pragma unroll
+  for (int i = 0; i < CPT; ++i) {
+    int ch;
+    attn_dual_stage_coord<D>(tid + i * 512, srow[i], ch);
+    soff[i] = attn_dual_off<D>(srow[i], ch);
+    srow[i] = srow[i] * 16 + ch;   // packed (row, ch)
+  }
+  auto half_load = [&](int kv0h) {
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      const int key = kv0h + (srow[i] >> 4);
+      const int d0 = (srow[i] & 15) * 8;
+      pk[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      pv[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (key < sk) {
+        const long src = kbase + (long)key * hk * D + d0;
+        pk[i] = *reinterpret_cast<const s16x8*>(K + src);
+        pv[i] = *reinterpret_cast<const s16x8*>(V + src);
+      }
+    }
+  };
+  auto half_store = [&](int buf, int half) {
+    char* dst = smem + buf * BUF_B + half * HALF_B;
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) {
+      *reinterpret_cast<s16x8*>(dst + soff[i]) = pk[i];
+      *reinterpret_cast<s16x8*>(dst + TILE_B + soff[i]) = pv[i];
+    }
+  };
+
+  if (t0 < t1) half_load(t0 * KVB);
 
   bf16x8 qfrag[NT], dofrag[NT];
   {
@@ -401,53 +528,41 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
   const float del_q =
       row_ok ? DELTA[((long)b * hq + h) * sq + qrow] : 0.f;
 
+  if (t0 < t1) {
+    half_store(0, 0);
+    half_load(t0 * KVB + 64);
+    half_store(0, 1);
+  }
+  __syncthreads();   // buffer 0 visible
+
   f32x16 dqacc[NA];
 #pragma unroll
   for (int a = 0; a < NA; ++a) dqacc[a] = f32x16(0.f);
 
-  int kv_hi_key = klimit;
-  if (CAUSAL) kv_hi_key = min(kv_hi_key, q0wg + 255 + shift + 1);
-  int kv_lo_key = 0;
-  if (HAS_WINDOW && wl >= 0) kv_lo_key = max(0, q0wg + shift - wl);
-  const int t0 = kv_lo_key / KVB;
-  const int t1 = (max(kv_hi_key, 0) + KVB - 1) / KVB;
+  // per-lane constant offsets into a K/V image: row reads (A operand, row =
+  // kb*32 + col, chunk 2t+hi) and the transposed-read bases of the
+  // dQ += dS K B operand K[key = kb*32 + 16tp + 8hi + j][d = 32a + col]
+  const unsigned row_off = attn_dual_off<D>(col, hi);
+  unsigned tr_b0, tr_b1;
+  attn_dual_tr_bases<D>(lane, tr_b0, tr_b1);
+  const unsigned lds_base = (unsigned)(size_t)smem;
 
-  const long kbase = ((long)b * sk * hk + kh) * D;
   for (int tile = t0; tile < t1; ++tile) {
     const int kv0 = tile * KVB;
-    {
-      constexpr int CHUNKS = KVB * D / 8;
-      for (int c = tid; c < CHUNKS; c += 512) {
-        const int row = c / (D / 8);
-        const int d0 = (c % (D / 8)) * 8;
-        const int key = kv0 + row;
-        s16x8 kv8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        s16x8 vv8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (key < sk) {
-          const long src = kbase + (long)key * hk * D + d0;
-          kv8 = *reinterpret_cast<const s16x8*>(K + src);
-          vv8 = *reinterpret_cast<const s16x8*>(V + src);
-        }
-        unsigned byte = row * (D * 2) + d0 * 2;
-        byte ^= (unsigned)((row & 7) << 4);
-        *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(k_lds) + byte) =
-            kv8;
-        *reinterpret_cast<s16x8*>(reinterpret_cast<char*>(v_lds) + byte) =
-            vv8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          unsigned tbyte = (unsigned)(d0 + j) * (KVB * 2) + row * 2;
-          tbyte ^= (unsigned)((((d0 + j) >> 3) & 7) << 4);
-          *reinterpret_cast<short*>(reinterpret_cast<char*>(kt_lds) +
-                                    tbyte) = kv8[j];
-        }
-      }
-    }
-    __syncthreads();
+    const int cur = (tile - t0) & 1;
+    const bool has_next = tile + 1 < t1;      // workgroup-uniform
 
 #pragma unroll 1
     for (int half = 0; half < KVB / 64; ++half) {
     const int kv0h = kv0 + half * 64;
+    // ---- issue the global loads of the next tile's same half -------------
+    if (has_next) half_load(kv0h + KVB);
+
+    const char* kcur = smem + cur * BUF_B + half * HALF_B;
+    const unsigned tr0 = lds_base + cur * BUF_B + half * HALF_B + tr_b0;
+    const unsigned tr1 = lds_base + cur * BUF_B + half * HALF_B + tr_b1;
+
+    // wave-uniform: EXEC is all ones at the transposed reads inside
     bool wave_active = kv0h < kv_hi_key;
     if (CAUSAL && kv0h > q0 + 31 + shift) wave_active = false;
     if (HAS_WINDOW && wl >= 0 && kv0h + 64 <= q0 + shift - wl)
@@ -465,13 +580,10 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
       for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          const int row = half * 64 + kb * 32 + col;
-          unsigned byte = row * (D * 2) + (t * 16 + hi * 8) * 2;
-          byte ^= (unsigned)((row & 7) << 4);
-          bf16x8 kf = *reinterpret_cast<const bf16x8*>(
-              reinterpret_cast<const char*>(k_lds) + byte);
-          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-              reinterpret_cast<const char*>(v_lds) + byte);
+          const unsigned byte = ((t & 1) ? (row_off ^ 32u) : row_off) +
+                                (t >> 1) * 512 + kb * 4 * (16 * D);
+          bf16x8 kf = *reinterpret_cast<const bf16x8*>(kcur + byte);
+          bf16x8 vf = *reinterpret_cast<const bf16x8*>(kcur + TILE_B + byte);
           s[kb] = AttnElem<FP16>::mfma(kf, qfrag[t], s[kb]);
           dp[kb] = AttnElem<FP16>::mfma(vf, dofrag[t], dp[kb]);
         }
@@ -492,28 +604,48 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
           dp[kb][r] = p * (dp[kb][r] - del_q) * scale;
         }
       }
-      // dQ[q][d] += dS[q][key] K[key][d]
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-        for (int tp = 0; tp < 2; ++tp) {
-          unsigned dsfr[4];
-          t12_pack_frag<AttnElem<FP16>>(dp[kb], tp, dsfr);
-          bf16x8 dsb = *reinterpret_cast<const bf16x8*>(dsfr);
-#pragma unroll
-          for (int a = 0; a < NA; ++a) {
-            const int d = a * 32 + col;
-            unsigned byte = (unsigned)d * (KVB * 2) +
-                            (half * 64 + kb * 32 + 16 * tp + hi * 8) * 2;
-            byte ^= (unsigned)(((d >> 3) & 7) << 4);
-            bf16x8 ktb = *reinterpret_cast<const bf16x8*>(
-                reinterpret_cast<const char*>(kt_lds) + byte);
-            dqacc[a] = AttnElem<FP16>::mfma(dsb, ktb, dqacc[a]);
-          }
-        }
+      // dQ[q][d] += dS[q][key] K[key][d]; the B operand comes from the same
+      // K image by ds_read_b64_tr_b16: tr0 (j = 0..3) / tr1 (j = 4..7)
+      // + (kb*4 + tp*2)*16*D + a*512 as the offset: immediate
+#define DQ_TR_STEP(kb_, tp_, a_)                                           \
+      {                                                                    \
+        attn_u32x2 kl_, kh_;                                               \
+        asm volatile(                                                      \
+            "ds_read_b64_tr_b16 %0, %2 offset:%c4\n\t"                   \
+            "ds_read_b64_tr_b16 %1, %3 offset:%c4\n\t"                   \
+            "s_waitcnt lgkmcnt(0)"                                         \
+            : "=v"(kl_), "=v"(kh_)                                         \
+            : "v"(tr0), "v"(tr1),                                          \
+              "i"(((kb_) * 4 + (tp_) * 2) * 16 * D + (a_) * 512));         \
+        attn_u32x4 uk_ = {kl_.x, kl_.y, kh_.x, kh_.y};                     \
+        bf16x8 ktb = __builtin_bit_cast(bf16x8, uk_);                      \
+        dqacc[a_] = AttnElem<FP16>::mfma(dsb, ktb, dqacc[a_]);             \
       }
+#define DQ_TR_ROW(kb_, tp_)                                                \
+      {                                                                    \
+        unsigned dsfr[4];                                                  \
+        t12_pack_frag<AttnElem<FP16>>(dp[kb_], tp_, dsfr);                 \
+        bf16x8 dsb = *reinterpret_cast<const bf16x8*>(dsfr);               \
+        DQ_TR_STEP(kb_, tp_, 0);                                           \
+        DQ_TR_STEP(kb_, tp_, 1);                                           \
+        if constexpr (NA > 2) {                                            \
+          DQ_TR_STEP(kb_, tp_, 2);                                         \
+          DQ_TR_STEP(kb_, tp_, 3);                                         \
+        }                                                                  \
+      }
+      DQ_TR_ROW(0, 0);
+      DQ_TR_ROW(0, 1);
+      DQ_TR_ROW(1, 0);
+      DQ_TR_ROW(1, 1);
+#undef DQ_TR_ROW
+#undef DQ_TR_STEP
     }
+    // ---- write the prefetched half to the OTHER buffer: all waves left it
+    // at the barrier that ended the previous tile --------------------------
+    if (has_next) half_store(cur ^ 1, half);
     }  // half
+    // one barrier per tile: publishes buffer cur^1 and retires this tile's
+    // reads of buffer cur before the next tile's writes to it
     __syncthreads();
   }
 
@@ -563,9 +695,10 @@ static void launch_fa_bwd(const torch::Tensor& dout, const torch::Tensor& q,
       (short*)dq.data_ptr(), b, sq, sk, hq, hk, scale, wl, wr, qlp, klp
 
   dim3 gkv((sk + 127) / 128, b * hk), bkv(256);
-  const int lds_kv = (2 * 32 * D + 128 * D) * 2 + 2 * 32 * 4;
+  // 2 x (Q + dO image) + V image + 2 x (lse + delta)
+  const int lds_kv = (4 * 32 * D + 128 * D) * 2 + 4 * 32 * 4;
   dim3 gq((sq + 255) / 256, b * hq), bq(512);
-  const int lds_q = 3 * 128 * D * 2;
+  const int lds_q = 4 * 128 * D * 2;   // 2 x (K image + V image)
 
 #define DISPATCH(C, W, L)                                                    \
   do {                                                                       \
@@ -619,19 +752,21 @@ std::vector<torch::Tensor> fa_backward(torch::Tensor dout, torch::Tensor q,
   auto delta = torch::empty_like(lse_c);
   {
     const long rows = (long)b * sq * hq;
-    const long grid = (rows + 3) / 4;
-    if (fp16)
-      hipLaunchKernelGGL(fa_bwd_preprocess_kernel<true>,
-                         dim3((unsigned)grid), dim3(256), 0, stream,
-                         (const short*)dout.data_ptr(),
-                         (const short*)out.data_ptr(),
-                         delta.data_ptr<float>(), b, sq, hq, D);
-    else
-      hipLaunchKernelGGL(fa_bwd_preprocess_kernel<false>,
-                         dim3((unsigned)grid), dim3(256), 0, stream,
-                         (const short*)dout.data_ptr(),
-                         (const short*)out.data_ptr(),
-                         delta.data_ptr<float>(), b, sq, hq, D);
+    // 4 waves per block, 64 / (D/8) rows per wave
+    const long rpb = 4 * (WAVE / (D / 8));
+    const long grid = (rows + rpb - 1) / rpb;
+#define PRE_LAUNCH(F, DD)                                                    \
+    hipLaunchKernelGGL((fa_bwd_preprocess_kernel<F, DD>),                    \
+                       dim3((unsigned)grid), dim3(256), 0, stream,           \
+                       (const short*)dout.data_ptr(),                        \
+                       (const short*)out.data_ptr(),                         \
+                       delta.data_ptr<float>(), b, sq, hq)
+    if (D == 128) {
+      if (fp16) PRE_LAUNCH(true, 128); else PRE_LAUNCH(false, 128);
+    } else {
+      if (fp16) PRE_LAUNCH(true, 64); else PRE_LAUNCH(false, 64);
+    }
+#undef PRE_LAUNCH
   }
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
