@@ -8,10 +8,13 @@ decode steps run single-query attention against the preallocated KV cache
 applied at absolute positions via table slices, and the logits come from
 one lm_head GEMM over the last position only.
 
-Decode currently materializes a contiguous copy of the live cache slice
-per step (the attention kernels take contiguous [b, s, h, d]); a
-batch-strided kernel path / paged KV layout is the next serving
-optimization.
+Decode steps (one new token) run ``flash_attn_with_kvcache``: a split-KV
+single-query kernel that reads the cache in place through its batch and
+sequence strides (no per-step copy of the live slice), serves all q heads
+of a kv head from one read of K/V, and bounds every load by the device-side
+length, so never-written cache slots cannot reach the result. Prefill keeps
+the full-tile flash attention. A paged (block-table) KV layout is the next
+serving step; it only replaces the kernel's address computation.
 
 Usage::
 
@@ -22,7 +25,7 @@ from typing import List, Optional
 
 import torch
 
-from ..ops.flash_attn import flash_attn_xla
+from ..ops.flash_attn import flash_attn_with_kvcache, flash_attn_xla
 from ..ops.rmsnorm import fused_add_rms_norm
 from ..ops.rope import apply_rotary_pos_emb
 
@@ -54,9 +57,13 @@ def _attn_with_cache(attn, x, cos, sin, cache: LayerKV, window=(-1, -1)):
     q, k = apply_rotary_pos_emb(q, k, cos, sin)
     cache.append(k, v)
     kc, vc = cache.view()
-    # bottom-right causal: the s new queries attend all cached keys up to
-    # their own position
-    o = flash_attn_xla(q, kc, vc, causal=True, window_size=window)
+    if s == 1:
+        # decode: the strided view is read in place, no copy
+        o = flash_attn_with_kvcache(q, kc, vc, window_size=(window[0], -1))
+    else:
+        # bottom-right causal: the s new queries attend all cached keys up
+        # to their own position
+        o = flash_attn_xla(q, kc, vc, causal=True, window_size=window)
     return attn.o_proj(o.reshape(b, s, h * attn.head_dim))
 
 
@@ -140,7 +147,8 @@ class GraphDecoder:
     with in-place KV writes, final norm, lm_head, argmax, and the in-graph
     position/length increments — into a hipGraph over STATIC shapes:
     attention runs against the full preallocated cache with a device-side
-    ``k_lens`` bound (the varlen kernel path), RoPE tables are gathered by
+    ``k_lens`` bound (the split-KV decode kernel cuts its key chunks from
+    that length on the device), RoPE tables are gathered by
     a device position index, and the next token feeds back into the input
     buffer inside the graph. Replaying the graph N times decodes N tokens
     with no host work in the loop (greedy only; sampling/eos use the eager
@@ -183,10 +191,9 @@ class GraphDecoder:
             q, k = apply_rotary_pos_emb(q, k, cos, sin)
             cache.k.index_copy_(1, self.pos, k)
             cache.v.index_copy_(1, self.pos, v)
-            from ..ops.flash_attn import FlashAttnFunc
-            o, _ = FlashAttnFunc.apply(
-                q, cache.k, cache.v, 0.0, attn.head_dim ** -0.5, True,
-                (-1, -1), None, False, None, self.k_lens)
+            o = flash_attn_with_kvcache(
+                q, cache.k, cache.v, cache_seqlens=self.k_lens,
+                softmax_scale=attn.head_dim ** -0.5)
             a = attn.o_proj(o.reshape(b, s, h * attn.head_dim))
             y2, resid2 = fused_add_rms_norm(
                 a, resid, layer.post_attention_layernorm.weight,

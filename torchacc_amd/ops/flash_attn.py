@@ -644,3 +644,156 @@ def flash_attn_kvpacked_xla(q, kv, dropout_p=0.0, softmax_scale=None,
     return flash_attn_xla(q, k, v, dropout_p, softmax_scale, causal,
                           window_size, alibi_slopes, deterministic,
                           return_attn_probs)
+
+
+# ---------------------------------------------------------------------------
+# decode: one query per sequence against an in-place KV cache
+# ---------------------------------------------------------------------------
+
+def _ref_decode(q, k_cache, v_cache, lens, softmax_scale, wl):
+    """fp32 reference for flash_attn_with_kvcache: batch i sees the keys
+    [lo_i, lens_i) with lo_i = max(0, lens_i - 1 - wl) (0 without a window).
+    Slots outside that range are dropped before any arithmetic, so their
+    contents (even NaN) cannot matter. Returns (out, lse[b, hq, 1])."""
+    b, _, hq, d = q.shape
+    cap, hk = k_cache.shape[1], k_cache.shape[2]
+    ik = torch.arange(cap, device=q.device).view(1, 1, 1, cap)
+    if lens is None:
+        klen = torch.full((b, 1, 1, 1), cap, device=q.device)
+    else:
+        klen = lens.long().clamp(0, cap).view(b, 1, 1, 1)
+    lo = (klen - 1 - wl).clamp(min=0) if wl >= 0 else torch.zeros_like(klen)
+    vis = (ik >= lo) & (ik < klen)                       # [b,1,1,cap]
+    keep = vis.view(b, 1, cap, 1)
+    zero = torch.zeros((), dtype=torch.float32, device=q.device)
+    qf = q.float().view(b, hk, hq // hk, d)              # head = kh*rep + r
+    kf = torch.where(keep, k_cache.float().permute(0, 2, 1, 3), zero)
+    vf = torch.where(keep, v_cache.float().permute(0, 2, 1, 3), zero)
+    scores = torch.matmul(qf, kf.transpose(-1, -2)) * softmax_scale
+    scores = scores.masked_fill(~vis, float("-inf"))
+    lse = torch.logsumexp(scores, dim=-1, keepdim=True)  # -inf if none seen
+    p = torch.where(torch.isfinite(lse), torch.exp(scores - lse), zero)
+    out = torch.matmul(p, vf)                            # [b,hk,rep,d]
+    return out.reshape(b, 1, hq, d).to(q.dtype), lse.reshape(b, hq, 1)
+
+
+_warned_decode = set()
+_NO_LENS = torch.empty(0)   # "no cache_seqlens" for ext.fa_decode
+
+
+def _decode_fallback_gpu(q, k_cache, v_cache, lens, softmax_scale, wl):
+    """GPU inputs the decode kernel does not cover (fp32, head dims other
+    than 64/128): the fixed-length attention path on a copy of the cache.
+    One batched call, without a host sync (so it still captures into a
+    graph), unless per-sequence lengths AND a window are given: a window
+    anchored at each live length has no batched form on that path, so that
+    case reads the lengths on the host and runs one call per sequence."""
+    key = (q.dtype, q.shape[-1])
+    if key not in _warned_decode:
+        _warned_decode.add(key)
+        from ..utils.logger import logger
+        logger.warning(
+            "flash_attn_with_kvcache: dtype %s / head_dim %d is not covered "
+            "by the decode kernel; using the fixed-length attention path on "
+            "a copy of the cache", *key)
+    b, _, hq, d = q.shape
+    cap = k_cache.shape[1]
+    if lens is None:
+        # sq = 1, bottom-right causal: the window is anchored at cap
+        return FlashAttnFunc.apply(q, k_cache, v_cache, 0.0, softmax_scale,
+                                   True, (wl, -1), None, False, None, None)
+    if wl < 0:
+        # the copy drops the slots past each length, so their contents
+        # cannot reach the fp32 composite as 0 * NaN either
+        keep = (torch.arange(cap, device=q.device).view(1, cap, 1, 1)
+                < lens.view(b, 1, 1, 1))
+        zero = torch.zeros((), dtype=q.dtype, device=q.device)
+        out, lse = FlashAttnFunc.apply(
+            q, torch.where(keep, k_cache, zero),
+            torch.where(keep, v_cache, zero), 0.0, softmax_scale, True,
+            (-1, -1), None, False, None, lens)
+        empty = (lens <= 0).view(b, 1, 1)
+        out = torch.where(empty.unsqueeze(-1), zero, out)
+        lse = torch.where(empty, torch.full_like(lse, float("-inf")), lse)
+        return out, lse
+    host_lens = [min(max(int(n), 0), cap) for n in lens.tolist()]
+    out = torch.zeros_like(q)
+    lse = torch.full((b, hq, 1), float("-inf"), dtype=torch.float32,
+                     device=q.device)
+    for i, n in enumerate(host_lens):
+        if n == 0:
+            continue
+        o_i, lse_i = FlashAttnFunc.apply(
+            q[i:i + 1], k_cache[i:i + 1, :n].contiguous(),
+            v_cache[i:i + 1, :n].contiguous(), 0.0, softmax_scale, True,
+            (wl, -1), None, False, None, None)
+        out[i:i + 1] = o_i
+        lse[i:i + 1] = lse_i
+    return out, lse
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
+                            softmax_scale=None, window_size=(-1, -1),
+                            num_splits=0, return_lse=False):
+    """Single-query (decode) attention over a KV cache, inference only.
+
+    q [b, 1, hq, d]; k_cache / v_cache [b, cap, hk, d] with hk | hq, read in
+    place: batch and sequence strides are arbitrary, only the last two dims
+    must be dense. ``cache_seqlens`` (int32/int64 [b], same device) gives the
+    live length per sequence (default: cap). The query of sequence i sits at
+    position len_i - 1 and sees keys [lo_i, len_i), lo_i = max(0, len_i - 1 -
+    window_size[0]) if window_size[0] >= 0 else 0. Slots outside that range
+    never influence the result, whatever they hold. len_i == 0 gives a zero
+    row and lse = -inf.
+
+    bf16/fp16 with d in {64, 128} on the GPU runs the split-KV HIP kernel
+    (csrc/flash_attn_decode.hip); ``num_splits`` = 0 lets the host pick the
+    number of key chunks from the shapes, a positive value forces it. That
+    path never syncs with the host. Other GPU inputs (fp32, other head dims)
+    run the fixed-length attention on a copy of the cache; this also stays
+    on the device, except with ``cache_seqlens`` and a window together,
+    which reads the lengths on the host and cannot be graph-captured.
+    Returns out [b, 1, hq, d], and lse [b, hq, 1] (fp32, natural log) with
+    ``return_lse``.
+    """
+    assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
+        "expected q [b, 1, hq, d] and caches [b, cap, hk, d]"
+    assert q.shape[1] == 1, \
+        f"flash_attn_with_kvcache takes one query per sequence, got {q.shape[1]}"
+    assert q.dtype == k_cache.dtype == v_cache.dtype
+    assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    assert q.device == k_cache.device == v_cache.device
+    assert k_cache.shape == v_cache.shape
+    assert q.shape[0] == k_cache.shape[0] and q.shape[3] == k_cache.shape[3]
+    assert q.shape[2] % k_cache.shape[2] == 0, "GQA requires h_k | h_q"
+    if torch.is_grad_enabled() and any(
+            t.requires_grad for t in (q, k_cache, v_cache)):
+        raise RuntimeError(
+            "flash_attn_with_kvcache is inference only (no backward); call "
+            "it under torch.no_grad() or detach the inputs")
+    lens = cache_seqlens
+    if lens is not None:
+        assert lens.dtype in (torch.int32, torch.int64), \
+            "cache_seqlens must be int32 or int64"
+        assert lens.shape == (q.shape[0],) and lens.device == q.device
+        if lens.dtype != torch.int32:
+            lens = lens.to(torch.int32)     # device-side cast, no sync
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    wl = int(window_size[0])
+
+    ext = dispatch(q)
+    if ext is None:
+        out, lse = _ref_decode(q, k_cache, v_cache, lens, softmax_scale, wl)
+    elif (q.dtype in (torch.float16, torch.bfloat16)
+          and q.shape[-1] in (64, 128)):
+        out, lse = ext.fa_decode(
+            q.contiguous(), k_cache, v_cache,
+            lens.contiguous() if lens is not None else _NO_LENS,
+            softmax_scale, wl, num_splits)
+    else:
+        out, lse = _decode_fallback_gpu(q, k_cache, v_cache, lens,
+                                        softmax_scale, wl)
+    if return_lse:
+        return out, lse
+    return out
