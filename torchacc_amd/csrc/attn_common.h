@@ -117,9 +117,49 @@ DEVINLINE attn_u32x2 attn_tr16_pair(unsigned a0, unsigned a1,
 //   transposed read, 32-lane half = 4 rows (row&3 = 0..3) x 4 chunks x 2
 //     8-byte halves -> 256 contiguous bytes mod 256.
 template <int D>
-DEVINLINE unsigned attn_dual_off(int row, int ch) {
+DEVINLINE constexpr unsigned attn_dual_off(int row, int ch) {
   return (unsigned)((row >> 3) * (16 * D) + (ch >> 2) * 512 +
                     (row & 7) * 64 + (((ch & 3) ^ ((row >> 2) & 3)) << 4));
+}
+
+// Inverse of attn_dual_off on 16-byte slots: slot s (byte offset 16*s of the
+// image) holds chunk ch of row `row`. A direct-to-LDS load writes wave base +
+// lane*16, i.e. consecutive slots, so the image is produced by giving lane l
+// the SOURCE address of (row, ch) = attn_dual_slot_coord(base_slot + l). 64
+// consecutive slots are two subtiles of the same 8 rows: 128 contiguous
+// global bytes per row.
+template <int D>
+DEVINLINE constexpr void attn_dual_slot_coord(int slot, int& row, int& ch) {
+  row = (slot / D) * 8 + ((slot >> 2) & 7);
+  ch = ((slot % D) >> 5) * 4 + ((slot & 3) ^ ((row >> 2) & 3));
+}
+
+// host-side check of the pair over every slot of a 128-row image
+template <int D>
+constexpr bool attn_dual_slot_coord_ok() {
+  for (int s = 0; s < 128 * D / 8; ++s) {
+    int row = 0, ch = 0;
+    attn_dual_slot_coord<D>(s, row, ch);
+    if (row < 0 || row >= 128 || ch < 0 || ch >= D / 8) return false;
+    if (attn_dual_off<D>(row, ch) != (unsigned)s * 16) return false;
+  }
+  return true;
+}
+static_assert(attn_dual_slot_coord_ok<64>() && attn_dual_slot_coord_ok<128>(),
+              "attn_dual_slot_coord must invert attn_dual_off");
+
+// Direct-to-LDS loads (global_load_lds_dwordx4 / _dword): lane l's bytes land
+// at lds_dst + l*16 (or l*4); lds_dst must be wave-uniform. Completion is
+// counted on vmcnt; a barrier after the wait publishes the data.
+DEVINLINE void attn_glds16(const void* gsrc, void* lds_dst) {
+  __builtin_amdgcn_global_load_lds(
+      (__attribute__((address_space(1))) void*)gsrc,
+      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+}
+DEVINLINE void attn_glds4(const void* gsrc, void* lds_dst) {
+  __builtin_amdgcn_global_load_lds(
+      (__attribute__((address_space(1))) void*)gsrc,
+      (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
 }
 
 // Staging order for the dual-use image: chunk index c -> (row, ch) such that

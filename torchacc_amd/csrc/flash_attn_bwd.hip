@@ -16,26 +16,38 @@
 // subtiles of 512 B with the 16-byte chunks of a row XORed by (row>>2)&3.
 // The same copy serves the row reads (ds_read_b128, A operand of S and dP)
 // and the transposed reads (ds_read_b64_tr_b16, B operand of dK, dV and dQ),
-// both conflict-free; the staging writes go in attn_dual_stage_coord order,
-// also conflict-free. There is no transposed K copy.
+// both conflict-free; register-staged writes (V in dkv, K/V in dq) go in
+// attn_dual_stage_coord order, also conflict-free. There is no transposed K
+// copy.
 //
 // Buffer rotation. Both kernels keep TWO staging buffers and one barrier per
 // tile. Iteration i computes from buffer i&1 and fills buffer (i+1)&1 with
 // tile i+1:
-//   dkv: at the top of the iteration (load + LDS write, then compute); the
-//        sweep over (head, q tile) is flattened so this runs across heads.
-//        Holding the tile in registers across the MFMA phases spills at
-//        D=128 (256 VGPRs, two workgroups per CU), so the overlap comes from
-//        the other waves and the second workgroup, which no longer meet a
-//        barrier between staging and compute.
+//   dkv: direct-to-LDS loads (global_load_lds, 16 bytes for Q and dO, 4 bytes
+//        for lse and delta) issued at the top of the iteration and waited
+//        for (vmcnt(0)) just before the closing barrier, so they are in
+//        flight over the whole compute phase and hold no registers (the
+//        kernel sits at the 256-VGPR budget of two workgroups per CU; a tile
+//        held in registers spills). The LDS destination of such a load is
+//        wave base + lane*16, so the image is kept and the swizzle is put on
+//        the per-lane source address (attn_dual_slot_coord). Rows beyond sq
+//        read the clamped row sq-1 and are masked like any row beyond
+//        qlimit. The compute phase consumes no ordinary global load, which
+//        would make the compiler drain vmcnt early. The sweep over (head, q
+//        tile) is flattened so the prefetch runs across heads.
 //   dq:  per 64-key half: global loads issued before the half's MFMAs, LDS
 //        write after them (16 VGPRs in flight).
 // The barrier that ends iteration i does both jobs: it publishes buffer
 // (i+1)&1 for iteration i+1, and it retires every wave's reads of buffer i&1
-// before iteration i+1 overwrites it. The writes of iteration i need no
+// before iteration i+1 overwrites it. The fills of iteration i need no
 // barrier of their own: buffer (i+1)&1 was last read in iteration i-1, whose
 // closing barrier every wave has passed. The prologue barrier publishes
 // buffer 0 (and the V image in dkv).
+//
+// Transposed reads. In both kernels the ds_read_b64_tr_b16 of the next step
+// (dkv: one (tp, a) step = 4 reads, 2 MFMAs) or of the next row of steps (dq:
+// NA steps of 2 reads, 1 MFMA each) are issued before the current step's
+// MFMAs; each step waits with a counted lgkmcnt for its own reads only.
 //
 // P is normalized against the stored global lse and delta comes from the
 // global (out, dout), so the same kernels serve per-block ring-attention
@@ -51,6 +63,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "attn_common.h"
+
+// s_waitcnt immediate for vmcnt(0) alone (gfx9 encoding: expcnt and lgkmcnt
+// fields at their maxima). Issued as the builtin so that the compiler's own
+// wait bookkeeping sees it.
+#define VMCNT0 0x0F70
 
 // ---------------------------------------------------------------------------
 // 1. preprocess: delta = rowsum(dO * O)   [b,h,sq] fp32
@@ -162,52 +179,40 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
   // across the head boundary
   const int n_tiles = qt1 > qt0 ? gqa * (qt1 - qt0) : 0;
 
-  // ---- staging of one Q/dO/lse/delta tile, split into a global-load half
-  // (into registers) and an LDS-write half ---------------------------------
-  s16x8 pq[CPT], pd[CPT];
-  float pst = 0.f;
-  auto tile_load = [&](int h, int q0) {
+  // ---- direct-to-LDS staging of one Q/dO/lse/delta tile into buffer `buf`.
+  // One wave-instruction writes 1 KiB = 64 consecutive 16-byte slots of an
+  // image (wave w, pass i: slots i*256 + w*64 ..), so the image stays the
+  // dual-use one and the swizzle goes on the per-lane SOURCE address
+  // (attn_dual_slot_coord, the inverse of attn_dual_off): 8 rows x 128
+  // contiguous bytes per instruction. Rows at or beyond sq read row sq-1:
+  // in bounds, finite, and masked by qrow < qlimit like every other row
+  // beyond the limit. lse (lanes 0..31) and delta (lanes 32..63) go the same
+  // way, one 4-byte instruction of wave 0, so that no ordinary global load is
+  // consumed while a tile is in flight (the compiler would drain vmcnt for
+  // it). Nothing is held in registers.
+  const int wid_s = __builtin_amdgcn_readfirstlane(wid);
+  auto tile_dma = [&](int h, int q0, int buf) {
+    char* dst = qd_lds + buf * BUF_B + wid_s * (WAVE * 16);
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       int row, ch;
-      attn_dual_stage_coord<D>(tid + i * 256, row, ch);
-      const int qrow = q0 + row;
-      pq[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      pd[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (qrow < sq) {
-        const long src = ((long)(b * sq + qrow) * hq + h) * D + ch * 8;
-        pq[i] = *reinterpret_cast<const s16x8*>(Q + src);
-        pd[i] = *reinterpret_cast<const s16x8*>(dOut + src);
-      }
+      attn_dual_slot_coord<D>(tid + i * 256, row, ch);
+      const int qrow = min(q0 + row, sq - 1);
+      const long src = ((long)(b * sq + qrow) * hq + h) * D + ch * 8;
+      attn_glds16(Q + src, dst + i * (256 * 16));
+      attn_glds16(dOut + src, dst + TILE_B + i * (256 * 16));
     }
-    if (tid < 2 * QT) {
-      // threads 0..QT-1 fetch lse, QT..2QT-1 fetch delta
-      const int qrow = q0 + (tid & (QT - 1));
-      const long idx = ((long)b * hq + h) * sq + min(qrow, sq - 1);
-      const float oob = tid < QT ? INFINITY : 0.f;
-      pst = (qrow < sq) ? (tid < QT ? LSE[idx] : DELTA[idx]) : oob;
+    if (wid_s == 0) {
+      const int qrow = min(q0 + (lane & (QT - 1)), sq - 1);
+      const long idx = ((long)b * hq + h) * sq + qrow;
+      attn_glds4(lane < QT ? LSE + idx : DELTA + idx,
+                 st_lds + buf * 2 * QT);
     }
-  };
-  auto tile_store = [&](int buf) {
-    char* dst = qd_lds + buf * BUF_B;
-    // the offsets are recomputed per tile from an opaque copy of tid: kept
-    // as loop invariants they would cost registers the MFMA phases need
-    int t_ = tid;
-    asm volatile("" : "+v"(t_));
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int row, ch;
-      attn_dual_stage_coord<D>(t_ + i * 256, row, ch);
-      const unsigned off = attn_dual_off<D>(row, ch);
-      *reinterpret_cast<s16x8*>(dst + off) = pq[i];
-      *reinterpret_cast<s16x8*>(dst + TILE_B + off) = pd[i];
-    }
-    if (tid < 2 * QT) st_lds[buf * 2 * QT + tid] = pst;
   };
 
   // loader position: (head, q tile) of the next tile to fetch
   int ld_gh = 0, ld_qt = qt0;
-  if (n_tiles > 0) tile_load(kh * gqa, qt0 * QT);
+  if (n_tiles > 0) tile_dma(kh * gqa, qt0 * QT, 0);
 
   // K fragments in registers; V staged once in LDS for the whole workgroup
   bf16x8 kfrag[NT];
@@ -239,7 +244,8 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
                                 attn_dual_off<D>(row, ch)) = vv8;
     }
   }
-  if (n_tiles > 0) tile_store(0);
+  // the direct-to-LDS loads of tile 0 are counted on vmcnt
+  __builtin_amdgcn_s_waitcnt(VMCNT0);
   __syncthreads();   // V image and buffer 0 visible
 
   // per-lane constant offsets into a Q image: row reads (A operand, row =
@@ -268,17 +274,15 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
     const int cur = it & 1;
     const int q0 = c_qt * QT;
     const bool has_next = it + 1 < n_tiles;   // workgroup-uniform
-    // ---- stage the next tile into the OTHER buffer before computing this
-    // one. Every wave left that buffer's reads behind at the barrier that
-    // ended the previous iteration, so no barrier is needed here, and a wave
-    // waiting for its loads does not hold up the waves (and the second
-    // resident workgroup) that are already in their MFMA phases. The staging
-    // registers are dead before the MFMA phases, which have no VGPR to spare
-    // (holding the tile in registers across them spills at D=128). ---------
+    // ---- issue the next tile's direct-to-LDS loads into the OTHER buffer
+    // before computing this one. Every wave left that buffer's reads behind
+    // at the barrier that ended the previous iteration, so no barrier is
+    // needed here. The loads stay in flight over the whole compute phase
+    // (which touches no global memory) and are waited for just before the
+    // closing barrier. ------------------------------------------------------
     if (has_next) {
       if (++ld_qt == qt1) { ld_qt = qt0; ++ld_gh; }
-      tile_load(kh * gqa + ld_gh, ld_qt * QT);
-      tile_store(cur ^ 1);
+      tile_dma(kh * gqa + ld_gh, ld_qt * QT, cur ^ 1);
     }
 
     const char* qcur = qd_lds + cur * BUF_B;
@@ -333,56 +337,76 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
       //   + tp*32*D + a*512 (+ TILE_B for dO)           (compile-time)
       // so all 4*NA reads of a tile use two address VGPRs + offset:
       // immediates.
-
-#define DKV_TR_STEP(tp_, a_)                                               \
+      //
+      // The 2*NA steps (tp, a) are software-pipelined: the four reads of
+      // step n+1 are issued before the two MFMAs of step n, and step n waits
+      // with lgkmcnt(4), i.e. for everything but the four reads just issued
+      // (LDS operations return in order; any other LDS or scalar-memory
+      // operation in flight only makes the counted wait stricter). The wait
+      // statement names the four destinations as in/out operands, so the
+      // MFMAs depend on it. Both A fragments are packed first: s and dp are
+      // dead from there on, which pays for the second set of destinations.
+#define DKV_TR_DECL(n_) attn_u32x2 ql##n_, qh##n_, dl##n_, dh##n_
+#define DKV_TR_ISSUE(n_, tp_, a_)                                          \
+      asm volatile(                                                        \
+          "ds_read_b64_tr_b16 %0, %4 offset:%c6\n\t"                     \
+          "ds_read_b64_tr_b16 %1, %5 offset:%c6\n\t"                     \
+          "ds_read_b64_tr_b16 %2, %4 offset:%c7\n\t"                     \
+          "ds_read_b64_tr_b16 %3, %5 offset:%c7"                          \
+          : "=v"(ql##n_), "=v"(qh##n_), "=v"(dl##n_), "=v"(dh##n_)         \
+          : "v"(tr0), "v"(tr1),                                            \
+            "i"((tp_) * 32 * D + (a_) * 512),                              \
+            "i"(TILE_B + (tp_) * 32 * D + (a_) * 512))
+#define DKV_TR_MFMA(n_, cnt_, a_, pb_, dsb_)                               \
       {                                                                    \
-        attn_u32x2 ql_, qh_, dl_, dh_;                                     \
-        asm volatile(                                                      \
-            "ds_read_b64_tr_b16 %0, %4 offset:%c6\n\t"                   \
-            "ds_read_b64_tr_b16 %1, %5 offset:%c6\n\t"                   \
-            "ds_read_b64_tr_b16 %2, %4 offset:%c7\n\t"                   \
-            "ds_read_b64_tr_b16 %3, %5 offset:%c7\n\t"                   \
-            "s_waitcnt lgkmcnt(0)"                                         \
-            : "=v"(ql_), "=v"(qh_), "=v"(dl_), "=v"(dh_)                   \
-            : "v"(tr0), "v"(tr1),                                          \
-              "i"((tp_) * 32 * D + (a_) * 512),                            \
-              "i"(TILE_B + (tp_) * 32 * D + (a_) * 512));                  \
-        attn_u32x4 uq_ = {ql_.x, ql_.y, qh_.x, qh_.y};                     \
-        attn_u32x4 ud_ = {dl_.x, dl_.y, dh_.x, dh_.y};                     \
+        asm volatile("s_waitcnt lgkmcnt(" #cnt_ ")"                        \
+                     : "+v"(ql##n_), "+v"(qh##n_), "+v"(dl##n_),           \
+                       "+v"(dh##n_));                                      \
+        attn_u32x4 uq_ = {ql##n_.x, ql##n_.y, qh##n_.x, qh##n_.y};         \
+        attn_u32x4 ud_ = {dl##n_.x, dl##n_.y, dh##n_.x, dh##n_.y};         \
         bf16x8 qbf = __builtin_bit_cast(bf16x8, uq_);                      \
         bf16x8 dob = __builtin_bit_cast(bf16x8, ud_);                      \
-        dvacc[a_] = AttnElem<FP16>::mfma(pb, dob, dvacc[a_]);              \
-        dkacc[a_] = AttnElem<FP16>::mfma(dsb, qbf, dkacc[a_]);             \
+        dvacc[a_] = AttnElem<FP16>::mfma(pb_, dob, dvacc[a_]);             \
+        dkacc[a_] = AttnElem<FP16>::mfma(dsb_, qbf, dkacc[a_]);            \
       }
-
-#pragma unroll
-      for (int tp = 0; tp < 2; ++tp) {
-        unsigned pfr[4], dsfr[4];
-        t12_pack_frag<AttnElem<FP16>>(s, tp, pfr);
-        t12_pack_frag<AttnElem<FP16>>(dp, tp, dsfr);
-        bf16x8 pb = *reinterpret_cast<const bf16x8*>(pfr);
-        bf16x8 dsb = *reinterpret_cast<const bf16x8*>(dsfr);
-        if (tp == 0) {
-          DKV_TR_STEP(0, 0);
-          DKV_TR_STEP(0, 1);
-          if constexpr (NA > 2) {
-            DKV_TR_STEP(0, 2);
-            DKV_TR_STEP(0, 3);
-          }
+      {
+        DKV_TR_DECL(0); DKV_TR_DECL(1); DKV_TR_DECL(2); DKV_TR_DECL(3);
+        DKV_TR_ISSUE(0, 0, 0);
+        unsigned pfr0[4], dsfr0[4], pfr1[4], dsfr1[4];
+        t12_pack_frag<AttnElem<FP16>>(s, 0, pfr0);
+        t12_pack_frag<AttnElem<FP16>>(dp, 0, dsfr0);
+        t12_pack_frag<AttnElem<FP16>>(s, 1, pfr1);
+        t12_pack_frag<AttnElem<FP16>>(dp, 1, dsfr1);
+        const bf16x8 pb0 = *reinterpret_cast<const bf16x8*>(pfr0);
+        const bf16x8 dsb0 = *reinterpret_cast<const bf16x8*>(dsfr0);
+        const bf16x8 pb1 = *reinterpret_cast<const bf16x8*>(pfr1);
+        const bf16x8 dsb1 = *reinterpret_cast<const bf16x8*>(dsfr1);
+        if constexpr (NA > 2) {
+          DKV_TR_DECL(4); DKV_TR_DECL(5); DKV_TR_DECL(6); DKV_TR_DECL(7);
+          DKV_TR_ISSUE(1, 0, 1); DKV_TR_MFMA(0, 4, 0, pb0, dsb0);
+          DKV_TR_ISSUE(2, 0, 2); DKV_TR_MFMA(1, 4, 1, pb0, dsb0);
+          DKV_TR_ISSUE(3, 0, 3); DKV_TR_MFMA(2, 4, 2, pb0, dsb0);
+          DKV_TR_ISSUE(4, 1, 0); DKV_TR_MFMA(3, 4, 3, pb0, dsb0);
+          DKV_TR_ISSUE(5, 1, 1); DKV_TR_MFMA(4, 4, 0, pb1, dsb1);
+          DKV_TR_ISSUE(6, 1, 2); DKV_TR_MFMA(5, 4, 1, pb1, dsb1);
+          DKV_TR_ISSUE(7, 1, 3); DKV_TR_MFMA(6, 4, 2, pb1, dsb1);
+          DKV_TR_MFMA(7, 0, 3, pb1, dsb1);
         } else {
-          DKV_TR_STEP(1, 0);
-          DKV_TR_STEP(1, 1);
-          if constexpr (NA > 2) {
-            DKV_TR_STEP(1, 2);
-            DKV_TR_STEP(1, 3);
-          }
+          DKV_TR_ISSUE(1, 0, 1); DKV_TR_MFMA(0, 4, 0, pb0, dsb0);
+          DKV_TR_ISSUE(2, 1, 0); DKV_TR_MFMA(1, 4, 1, pb0, dsb0);
+          DKV_TR_ISSUE(3, 1, 1); DKV_TR_MFMA(2, 4, 0, pb1, dsb1);
+          DKV_TR_MFMA(3, 0, 1, pb1, dsb1);
         }
       }
-#undef DKV_TR_STEP
+#undef DKV_TR_DECL
+#undef DKV_TR_ISSUE
+#undef DKV_TR_MFMA
     }  // wave_active
 
-    // one barrier per tile: it publishes buffer cur^1 and retires this
-    // iteration's reads of buffer cur before the next iteration writes it
+    // one barrier per tile: it publishes buffer cur^1 (whose direct-to-LDS
+    // loads every wave has waited for) and retires this iteration's reads of
+    // buffer cur before the next iteration's loads overwrite it
+    __builtin_amdgcn_s_waitcnt(VMCNT0);
     __syncthreads();
     if (++c_qt == qt1) c_qt = qt0;
     const unsigned hop = cur ? (unsigned)-BUF_B : (unsigned)BUF_B;
@@ -607,38 +631,82 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
       // dQ[q][d] += dS[q][key] K[key][d]; the B operand comes from the same
       // K image by ds_read_b64_tr_b16: tr0 (j = 0..3) / tr1 (j = 4..7)
       // + (kb*4 + tp*2)*16*D + a*512 as the offset: immediate
-#define DQ_TR_STEP(kb_, tp_, a_)                                           \
+      //
+      // Software-pipelined like the dkv steps, NA reads (one row of steps,
+      // (kb, tp) fixed) ahead: the reads of row r+1 are issued one per step
+      // of row r, before that step's MFMA, and each step waits with a
+      // counted lgkmcnt for its own pair only. The wait statement names the
+      // pair as in/out operands, so the MFMA depends on it.
+#define DQ_TR_DECL(n_) attn_u32x2 kl##n_, kh##n_
+#define DQ_TR_ISSUE(n_, kb_, tp_, a_)                                      \
+      asm volatile(                                                        \
+          "ds_read_b64_tr_b16 %0, %2 offset:%c4\n\t"                     \
+          "ds_read_b64_tr_b16 %1, %3 offset:%c4"                          \
+          : "=v"(kl##n_), "=v"(kh##n_)                                     \
+          : "v"(tr0), "v"(tr1),                                            \
+            "i"(((kb_) * 4 + (tp_) * 2) * 16 * D + (a_) * 512))
+#define DQ_TR_MFMA(n_, cnt_, a_, dsb_)                                     \
       {                                                                    \
-        attn_u32x2 kl_, kh_;                                               \
-        asm volatile(                                                      \
-            "ds_read_b64_tr_b16 %0, %2 offset:%c4\n\t"                   \
-            "ds_read_b64_tr_b16 %1, %3 offset:%c4\n\t"                   \
-            "s_waitcnt lgkmcnt(0)"                                         \
-            : "=v"(kl_), "=v"(kh_)                                         \
-            : "v"(tr0), "v"(tr1),                                          \
-              "i"(((kb_) * 4 + (tp_) * 2) * 16 * D + (a_) * 512));         \
-        attn_u32x4 uk_ = {kl_.x, kl_.y, kh_.x, kh_.y};                     \
+        asm volatile("s_waitcnt lgkmcnt(" #cnt_ ")"                        \
+                     : "+v"(kl##n_), "+v"(kh##n_));                        \
+        attn_u32x4 uk_ = {kl##n_.x, kl##n_.y, kh##n_.x, kh##n_.y};         \
         bf16x8 ktb = __builtin_bit_cast(bf16x8, uk_);                      \
-        dqacc[a_] = AttnElem<FP16>::mfma(dsb, ktb, dqacc[a_]);             \
+        dqacc[a_] = AttnElem<FP16>::mfma(dsb_, ktb, dqacc[a_]);            \
       }
-#define DQ_TR_ROW(kb_, tp_)                                                \
-      {                                                                    \
-        unsigned dsfr[4];                                                  \
-        t12_pack_frag<AttnElem<FP16>>(dp[kb_], tp_, dsfr);                 \
-        bf16x8 dsb = *reinterpret_cast<const bf16x8*>(dsfr);               \
-        DQ_TR_STEP(kb_, tp_, 0);                                           \
-        DQ_TR_STEP(kb_, tp_, 1);                                           \
-        if constexpr (NA > 2) {                                            \
-          DQ_TR_STEP(kb_, tp_, 2);                                         \
-          DQ_TR_STEP(kb_, tp_, 3);                                         \
-        }                                                                  \
+#define DQ_PACK(r_, kb_, tp_)                                              \
+      unsigned dsfr##r_[4];                                                \
+      t12_pack_frag<AttnElem<FP16>>(dp[kb_], tp_, dsfr##r_);               \
+      const bf16x8 dsb##r_ = *reinterpret_cast<const bf16x8*>(dsfr##r_)
+      if constexpr (NA > 2) {
+        // step n = 4*row + a, row = 2*kb + tp; NA = 4 pairs (8 reads) ahead
+        DQ_TR_DECL(0); DQ_TR_DECL(1); DQ_TR_DECL(2); DQ_TR_DECL(3);
+        DQ_TR_DECL(4); DQ_TR_DECL(5); DQ_TR_DECL(6); DQ_TR_DECL(7);
+        DQ_TR_DECL(8); DQ_TR_DECL(9); DQ_TR_DECL(10); DQ_TR_DECL(11);
+        DQ_TR_DECL(12); DQ_TR_DECL(13); DQ_TR_DECL(14); DQ_TR_DECL(15);
+        DQ_TR_ISSUE(0, 0, 0, 0); DQ_TR_ISSUE(1, 0, 0, 1);
+        DQ_TR_ISSUE(2, 0, 0, 2); DQ_TR_ISSUE(3, 0, 0, 3);
+        DQ_PACK(0, 0, 0);
+        DQ_TR_ISSUE(4, 0, 1, 0); DQ_TR_MFMA(0, 8, 0, dsb0);
+        DQ_TR_ISSUE(5, 0, 1, 1); DQ_TR_MFMA(1, 8, 1, dsb0);
+        DQ_TR_ISSUE(6, 0, 1, 2); DQ_TR_MFMA(2, 8, 2, dsb0);
+        DQ_TR_ISSUE(7, 0, 1, 3); DQ_TR_MFMA(3, 8, 3, dsb0);
+        DQ_PACK(1, 0, 1);
+        DQ_TR_ISSUE(8, 1, 0, 0); DQ_TR_MFMA(4, 8, 0, dsb1);
+        DQ_TR_ISSUE(9, 1, 0, 1); DQ_TR_MFMA(5, 8, 1, dsb1);
+        DQ_TR_ISSUE(10, 1, 0, 2); DQ_TR_MFMA(6, 8, 2, dsb1);
+        DQ_TR_ISSUE(11, 1, 0, 3); DQ_TR_MFMA(7, 8, 3, dsb1);
+        DQ_PACK(2, 1, 0);
+        DQ_TR_ISSUE(12, 1, 1, 0); DQ_TR_MFMA(8, 8, 0, dsb2);
+        DQ_TR_ISSUE(13, 1, 1, 1); DQ_TR_MFMA(9, 8, 1, dsb2);
+        DQ_TR_ISSUE(14, 1, 1, 2); DQ_TR_MFMA(10, 8, 2, dsb2);
+        DQ_TR_ISSUE(15, 1, 1, 3); DQ_TR_MFMA(11, 8, 3, dsb2);
+        DQ_PACK(3, 1, 1);
+        DQ_TR_MFMA(12, 6, 0, dsb3);
+        DQ_TR_MFMA(13, 4, 1, dsb3);
+        DQ_TR_MFMA(14, 2, 2, dsb3);
+        DQ_TR_MFMA(15, 0, 3, dsb3);
+      } else {
+        // step n = 2*row + a; NA = 2 pairs (4 reads) ahead
+        DQ_TR_DECL(0); DQ_TR_DECL(1); DQ_TR_DECL(2); DQ_TR_DECL(3);
+        DQ_TR_DECL(4); DQ_TR_DECL(5); DQ_TR_DECL(6); DQ_TR_DECL(7);
+        DQ_TR_ISSUE(0, 0, 0, 0); DQ_TR_ISSUE(1, 0, 0, 1);
+        DQ_PACK(0, 0, 0);
+        DQ_TR_ISSUE(2, 0, 1, 0); DQ_TR_MFMA(0, 4, 0, dsb0);
+        DQ_TR_ISSUE(3, 0, 1, 1); DQ_TR_MFMA(1, 4, 1, dsb0);
+        DQ_PACK(1, 0, 1);
+        DQ_TR_ISSUE(4, 1, 0, 0); DQ_TR_MFMA(2, 4, 0, dsb1);
+        DQ_TR_ISSUE(5, 1, 0, 1); DQ_TR_MFMA(3, 4, 1, dsb1);
+        DQ_PACK(2, 1, 0);
+        DQ_TR_ISSUE(6, 1, 1, 0); DQ_TR_MFMA(4, 4, 0, dsb2);
+        DQ_TR_ISSUE(7, 1, 1, 1); DQ_TR_MFMA(5, 4, 1, dsb2);
+        DQ_PACK(3, 1, 1);
+        DQ_TR_MFMA(6, 2, 0, dsb3);
+        DQ_TR_MFMA(7, 0, 1, dsb3);
       }
-      DQ_TR_ROW(0, 0);
-      DQ_TR_ROW(0, 1);
-      DQ_TR_ROW(1, 0);
-      DQ_TR_ROW(1, 1);
-#undef DQ_TR_ROW
-#undef DQ_TR_STEP
+#undef DQ_PACK
+#undef DQ_TR_DECL
+#undef DQ_TR_ISSUE
+#undef DQ_TR_MFMA
     }
     // ---- write the prefetched half to the OTHER buffer: all waves left it
     // at the barrier that ended the previous tile --------------------------
