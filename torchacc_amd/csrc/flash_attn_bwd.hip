@@ -49,6 +49,18 @@
 // NA steps of 2 reads, 1 MFMA each) are issued before the current step's
 // MFMAs; each step waits with a counted lgkmcnt for its own reads only.
 //
+// Two softmax bodies in dkv. Between the S/dP MFMAs and the dV/dK steps a
+// wave picks, per tile and wave-uniformly, how P and dS are computed: the
+// INTERIOR body when all 32 rows and 32 keys are inside the limits, the block
+// lies wholly on the visible side of the causal diagonal and all 32 staged
+// lse are finite (one class compare + ballot); the general body, with the
+// per-element `valid` mask, otherwise. Both evaluate the same expressions,
+// so the choice changes no bit. The instruction order of a tile is
+// unchanged: 16 MFMAs (S, dP interleaved over t), the softmax block, 16
+// MFMAs (dV, dK). Window and lens instantiations, and fa_bwd_dq, have the
+// general body only (the second body costs them registers: see
+// profiles/r06_attn_bwd_valu.md).
+//
 // P is normalized against the stored global lse and delta comes from the
 // global (out, dout), so the same kernels serve per-block ring-attention
 // backward unchanged.
@@ -62,6 +74,7 @@
 // transposes the accumulator into an A/B operand.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <type_traits>
 #include "attn_common.h"
 
 // s_waitcnt immediate for vmcnt(0) alone (gfx9 encoding: expcnt and lgkmcnt
@@ -191,6 +204,7 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
   // consumed while a tile is in flight (the compiler would drain vmcnt for
   // it). Nothing is held in registers.
   const int wid_s = __builtin_amdgcn_readfirstlane(wid);
+  const int key_s = kv0wg + wid_s * 32;   // key_b, provably wave-uniform
   auto tile_dma = [&](int h, int q0, int buf) {
     char* dst = qd_lds + buf * BUF_B + wid_s * (WAVE * 16);
 #pragma unroll
@@ -313,21 +327,60 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
         dp = AttnElem<FP16>::mfma(df, vf, dp);
       }
       // P = exp(S*scale - lse); dS = P*(dP - delta)*scale
-      // (s reused as P, dp reused as dS — register budget)
+      // (s reused as P, dp reused as dS — register budget), in two
+      // instantiations. INTERIOR: every (q row, key) pair of the wave's
+      // 32 x 32 block is valid, so there is no compare, no select and no
+      // `valid` logic; the expressions are those of the general body, which
+      // serves the edge tiles.
+      auto softmax = [&](auto interior_c) {
+      constexpr bool INTERIOR = decltype(interior_c)::value;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int qrow = q0 + CROW(r, hi);
         const float lse_q = lse_lds[CROW(r, hi)];
         const float del_q = del_lds[CROW(r, hi)];
-        bool valid =
-            (qrow < qlimit) && (mykey < klimit) && isfinite(lse_q);
-        if (CAUSAL) valid &= (mykey <= qrow + shift);
-        if (HAS_WINDOW && wl >= 0) valid &= (mykey >= qrow + shift - wl);
-        if (HAS_WINDOW && wr >= 0 && !CAUSAL)
-          valid &= (mykey <= qrow + shift + wr);
-        const float p = valid ? __expf(s[r] * scale - lse_q) : 0.f;
+        float p;
+        if constexpr (INTERIOR) {
+          p = __expf(s[r] * scale - lse_q);
+        } else {
+          bool valid =
+              (qrow < qlimit) && (mykey < klimit) && isfinite(lse_q);
+          if (CAUSAL) valid &= (mykey <= qrow + shift);
+          if (HAS_WINDOW && wl >= 0) valid &= (mykey >= qrow + shift - wl);
+          if (HAS_WINDOW && wr >= 0 && !CAUSAL)
+            valid &= (mykey <= qrow + shift + wr);
+          p = valid ? __expf(s[r] * scale - lse_q) : 0.f;
+        }
+        float ds = p * (dp[r] - del_q) * scale;
+        if constexpr (INTERIOR) {
+          // Keep the scalar v_sub/v_mul forms: without the selects between
+          // them the SLP vectorizer would pair these into v_pk_*_f32, which
+          // run slower beside MFMAs. An opaque value is no vectorizer seed.
+          asm("" : "+v"(ds));
+        }
         s[r] = p;
-        dp[r] = p * (dp[r] - del_q) * scale;
+        dp[r] = ds;
+      }
+      };
+      // wave-uniform choice of the body: all 32 rows and all 32 keys inside
+      // the limits, the whole block on the visible side of the diagonal and
+      // of the window, and all 32 staged lse finite (lane l tests row l&31)
+      //
+      // Only the instantiations without window and without lens carry the
+      // second body: with it the D=64 window ones need 170 VGPRs (occupancy
+      // 3 -> 2) and the D=128 causal + lens ones spill 8 bytes. The others
+      // compile to what they were.
+      if constexpr (!HAS_WINDOW && !HAS_LENS) {
+        bool interior = (q0 + QT <= qlimit) && (key_s + 32 <= klimit);
+        if (CAUSAL) interior = interior && (key_s + 31 <= q0 + shift);
+        interior = interior &&
+            __builtin_amdgcn_ballot_w64(isfinite(lse_lds[col])) == ~0ull;
+        if (interior)
+          softmax(std::true_type{});
+        else
+          softmax(std::false_type{});
+      } else {
+        softmax(std::false_type{});
       }
       // A-frags over the q k-dim; step tp covers q rows 16tp..16tp+15.
       // B-frags X[q = 16tp + hi*8 + jj][d = a*32 + col] come straight from
