@@ -72,6 +72,13 @@ std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
                                      torch::Tensor k_lens,
                                      double softmax_scale, long wl,
                                      long num_splits);
+std::vector<torch::Tensor> fa_decode_paged(torch::Tensor q,
+                                           torch::Tensor k_cache,
+                                           torch::Tensor v_cache,
+                                           torch::Tensor k_lens,
+                                           torch::Tensor block_table,
+                                           double softmax_scale, long wl,
+                                           long num_splits);
 
 // gemm.hip (hipBLASLt tuned GEMM)
 std::vector<int64_t> lt_gemm_candidates(int64_t m, int64_t n, int64_t k,
@@ -100,6 +107,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_varlen_forward", &fa_varlen_forward);
   m.def("fa_varlen_backward", &fa_varlen_backward);
   m.def("fa_decode", &fa_decode);
+  m.def("fa_decode_paged", &fa_decode_paged);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);
   m.def("lt_gemm", &lt_gemm, pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("ta"), pybind11::arg("tb"),

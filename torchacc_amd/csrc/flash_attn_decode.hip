@@ -32,6 +32,17 @@
 // Masking: keys outside [lo, klen) are never loaded (their registers are
 // zero) and their scores are -inf, so whatever lies in unwritten cache slots
 // cannot reach the result, not even as 0 * NaN.
+//
+// Paged variant (PAGED = true): K and V are page pools [num_pages,
+// page_size, hk, d] and block_table[b][key >> shift] names the physical page
+// of a logical key. Only the address computation differs: slot, dofs, the
+// tile loop, the split chunks and every arithmetic step are the contiguous
+// kernel's, so the result is bitwise the contiguous kernel's on the gathered
+// cache at the same num_splits. The table entries of a tile are fetched one
+// tile before its K/V loads are issued (two tiles before they are used), so
+// no table read sits in front of a K/V prefetch inside the loop; only
+// entries of keys < end are read (never those of logical pages past the
+// live length), and each is clamped into [0, num_pages - 1] before use.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
@@ -71,7 +82,7 @@ DEVINLINE float dec_group_sum(float v) {
 
 // In HIP the second launch-bounds argument is the minimum number of waves
 // per execution unit (SIMD), not blocks per CU: 2 gives a 256-VGPR budget.
-template <int D, int R, bool FP16>
+template <int D, int R, bool FP16, bool PAGED>
 __global__ __launch_bounds__(DEC_THREADS, 2)
 void fa_decode_split_kernel(const short* __restrict__ Q,
                             const short* __restrict__ K,
@@ -82,7 +93,11 @@ void fa_decode_split_kernel(const short* __restrict__ Q,
                             float* __restrict__ lse_part, int cap, int hq,
                             int hk, long k_sb, long k_ss, long v_sb,
                             long v_ss, float scale_log2, int wl,
-                            int num_splits) {
+                            int num_splits,
+                            // PAGED only: k_sb / v_sb are the page strides,
+                            // cap = table_width << page_shift
+                            const int* __restrict__ block_table,
+                            int page_shift, int num_pages) {
   using ET = AttnElem<FP16>;
   constexpr int LPK = D / 8;          // lanes per key
   constexpr int KPW = 64 / LPK;       // keys per wave per load
@@ -142,17 +157,40 @@ void fa_decode_split_kernel(const short* __restrict__ Q,
     for (int j = 0; j < 8; ++j) q[r][j] = ET::to_f32(v[j]) * scale_log2;
   }
 
-  const short* kp = K + (long)b * k_sb + (long)kh * D + dofs;
-  const short* vp = V + (long)b * v_sb + (long)kh * D + dofs;
+  const short* kp = K + (PAGED ? 0L : (long)b * k_sb) + (long)kh * D + dofs;
+  const short* vp = V + (PAGED ? 0L : (long)b * v_sb) + (long)kh * D + dofs;
+
+  // PAGED: this sequence's table row, and the clamped physical pages of the
+  // U keys a lane owns in a tile. Entries are read for keys < end only, i.e.
+  // for logical pages < ceil(len / page_size): a lane whose key lies past
+  // the chunk reads the entry of key end - 1 instead (begin < end here), so
+  // the load needs no branch and the U loads of a tile issue back to back.
+  const int* bt = PAGED ? block_table + (long)b * (cap >> page_shift) : nullptr;
+  auto load_pages = [&](int key0, int* pg) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int key = min(key0 + u * S + slot, end - 1);
+      pg[u] = min(max(bt[key >> page_shift], 0), num_pages - 1);
+    }
+  };
 
   // keys outside [begin, end) are not loaded: their registers are zero
-  auto load_tile = [&](const short* base, long ss, int key0, s16x8* reg) {
+  auto load_tile = [&](const short* base, long sb, long ss, int key0,
+                       const int* pg, s16x8* reg) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int key = key0 + u * S + slot;
-      reg[u] = (key < end)
-                   ? *reinterpret_cast<const s16x8*>(base + (long)key * ss)
-                   : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if constexpr (PAGED) {
+        const int in_page = key & ((1 << page_shift) - 1);
+        reg[u] = (key < end)
+                     ? *reinterpret_cast<const s16x8*>(
+                           base + (long)pg[u] * sb + (long)in_page * ss)
+                     : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      } else {
+        reg[u] = (key < end)
+                     ? *reinterpret_cast<const s16x8*>(base + (long)key * ss)
+                     : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      }
     }
   };
 
@@ -166,10 +204,16 @@ void fa_decode_split_kernel(const short* __restrict__ Q,
   }
 
   s16x8 kreg[U], vreg[U];
-  load_tile(kp, k_ss, begin, kreg);
-  load_tile(vp, v_ss, begin, vreg);
+  // pg: pages of the tile whose K/V are loaded next; pg_ahead: the tile
+  // after that, in flight while this tile computes (PAGED only)
+  int pg[U], pg_ahead[U];
+  if constexpr (PAGED) load_pages(begin, pg);
+  load_tile(kp, k_sb, k_ss, begin, pg, kreg);
+  load_tile(vp, v_sb, v_ss, begin, pg, vreg);
+  if constexpr (PAGED) load_pages(begin + DEC_TK, pg);
 
   for (int kt = begin; kt < end; kt += DEC_TK) {
+    if constexpr (PAGED) load_pages(kt + 2 * DEC_TK, pg_ahead);
     // ---- scores: s[r][u] = q[r] . K[key_u], log2 domain ------------------
     float s[R][U];
 #pragma unroll
@@ -186,7 +230,7 @@ void fa_decode_split_kernel(const short* __restrict__ Q,
       }
     }
     // K registers are free: the next tile's K flies under softmax and PV
-    load_tile(kp, k_ss, kt + DEC_TK, kreg);
+    load_tile(kp, k_sb, k_ss, kt + DEC_TK, pg, kreg);
 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -231,7 +275,11 @@ void fa_decode_split_kernel(const short* __restrict__ Q,
         for (int j = 0; j < 8; ++j)
           acc[r][j] = fmaf(s[r][u], vf[j], acc[r][j]);
     }
-    load_tile(vp, v_ss, kt + DEC_TK, vreg);
+    load_tile(vp, v_sb, v_ss, kt + DEC_TK, pg, vreg);
+    if constexpr (PAGED) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) pg[u] = pg_ahead[u];
+    }
   }
 
   // ---- merge the key groups of a wave (fixed butterfly order) ------------
@@ -340,22 +388,28 @@ int choose_num_splits(int b, int hk_groups, int cap, int num_cus) {
   return (int)std::max<long>(s, 1);
 }
 
-template <int D, int R, bool FP16>
+// Contiguous: k / v are [b, cap, hk, d] and bt is null. Paged: k / v are
+// pools [num_pages, page_size, hk, d], bt is the [b, cap >> page_shift]
+// table; the strides handed to the kernel are then the page and slot strides.
+template <int D, int R, bool FP16, bool PAGED>
 void launch_decode(const torch::Tensor& q, const torch::Tensor& k,
                    const torch::Tensor& v, const int* klp, torch::Tensor& o,
                    torch::Tensor& lse, float* o_part, float* lse_part,
                    float scale_log2, int wl, int num_splits, int groups,
-                   hipStream_t stream) {
+                   hipStream_t stream, int cap, const int* bt,
+                   int page_shift) {
   const int b = q.size(0), hq = q.size(2);
-  const int cap = k.size(1), hk = k.size(2);
+  const int hk = k.size(2);
+  const int num_pages = PAGED ? (int)k.size(0) : 0;
   dim3 grid(num_splits, hk * groups, b);
-  hipLaunchKernelGGL((fa_decode_split_kernel<D, R, FP16>), grid,
+  hipLaunchKernelGGL((fa_decode_split_kernel<D, R, FP16, PAGED>), grid,
                      dim3(DEC_THREADS), 0, stream,
                      (const short*)q.data_ptr(), (const short*)k.data_ptr(),
                      (const short*)v.data_ptr(), klp, (short*)o.data_ptr(),
                      lse.data_ptr<float>(), o_part, lse_part, cap, hq, hk,
                      (long)k.stride(0), (long)k.stride(1), (long)v.stride(0),
-                     (long)v.stride(1), scale_log2, wl, num_splits);
+                     (long)v.stride(1), scale_log2, wl, num_splits, bt,
+                     page_shift, num_pages);
   if (num_splits > 1) {
     hipLaunchKernelGGL((fa_decode_combine_kernel<D, FP16>), dim3(b * hq),
                        dim3(D), 0, stream, o_part, lse_part,
@@ -377,40 +431,43 @@ void check_cache(const torch::Tensor& c, const torch::Tensor& q,
               "fa_decode: ", name, " rows must be 16-byte aligned");
 }
 
-}  // namespace
-
-std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
-                                     torch::Tensor v_cache,
-                                     torch::Tensor k_lens,
-                                     double softmax_scale, long wl,
-                                     long num_splits) {
+void check_q(const torch::Tensor& q) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.is_contiguous() &&
                   q.size(1) == 1,
               "fa_decode: q must be a contiguous GPU [b, 1, hq, d]");
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 ||
                   q.scalar_type() == torch::kHalf,
               "fa_decode: bf16/fp16 only");
-  check_cache(k_cache, q, "k_cache");
-  check_cache(v_cache, q, "v_cache");
-  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
-              "fa_decode: k_cache and v_cache shapes differ");
+}
+
+const int* check_lens(const torch::Tensor& k_lens, long b) {
+  TORCH_CHECK(k_lens.is_cuda() && k_lens.scalar_type() == torch::kInt32 &&
+                  k_lens.dim() == 1 && k_lens.size(0) == b &&
+                  k_lens.is_contiguous(),
+              "fa_decode: k_lens must be a GPU int32 [b]");
+  return k_lens.data_ptr<int>();
+}
+
+// Shared tail of fa_decode / fa_decode_paged: shape checks that hold for
+// both layouts, split choice, workspace, launches. `cap` is the contiguous
+// capacity or table_width * page_size; hk = k.size(2) in both layouts.
+template <bool PAGED>
+std::vector<torch::Tensor> run_decode(const torch::Tensor& q,
+                                      const torch::Tensor& k_cache,
+                                      const torch::Tensor& v_cache,
+                                      const int* klp, long cap,
+                                      const int* bt, int page_shift,
+                                      double softmax_scale, long wl,
+                                      long num_splits) {
   const long b = q.size(0), hq = q.size(2), D = q.size(3);
-  const long cap = k_cache.size(1), hk = k_cache.size(2);
+  const long hk = k_cache.size(2);
   TORCH_CHECK(D == 64 || D == 128, "fa_decode: head_dim must be 64 or 128");
-  TORCH_CHECK(k_cache.size(0) == b && k_cache.size(3) == D);
+  TORCH_CHECK(k_cache.size(3) == D);
   TORCH_CHECK(hk > 0 && hq % hk == 0, "fa_decode: needs h_k | h_q");
   TORCH_CHECK(b >= 1 && b <= 65535 && cap >= 1 && cap <= (1L << 30));
   TORCH_CHECK(num_splits >= 0 && num_splits <= 65535,
               "fa_decode: num_splits must be in [0, 65535]");
   wl = std::min<long>(wl, 1L << 30);  // anything larger is "no window"
-  const int* klp = nullptr;
-  if (k_lens.numel() > 0) {
-    TORCH_CHECK(k_lens.is_cuda() && k_lens.scalar_type() == torch::kInt32 &&
-                    k_lens.dim() == 1 && k_lens.size(0) == b &&
-                    k_lens.is_contiguous(),
-                "fa_decode: k_lens must be a GPU int32 [b]");
-    klp = k_lens.data_ptr<int>();
-  }
 
   const int rep = hq / hk;
   const int groups = (rep + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
@@ -436,9 +493,9 @@ std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
 
 #define DEC_LAUNCH(DD, RR)                                                   \
   FP16_SWITCH(q.scalar_type() == torch::kHalf,                               \
-              launch_decode<DD, RR, kFP16>(q, k_cache, v_cache, klp, o, lse, \
-                                           opp, lpp, scale_log2, (int)wl,    \
-                                           ns, groups, stream))
+              launch_decode<DD, RR, kFP16, PAGED>(                           \
+                  q, k_cache, v_cache, klp, o, lse, opp, lpp, scale_log2,    \
+                  (int)wl, ns, groups, stream, (int)cap, bt, page_shift))
 #define DEC_ROWS(DD)                                                         \
   do {                                                                       \
     if (rep == 1) DEC_LAUNCH(DD, 1);                                         \
@@ -452,3 +509,64 @@ std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
   HIP_CHECK_LAST();
   return {o, lse};
 }
+
+}  // namespace
+
+std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
+                                     torch::Tensor v_cache,
+                                     torch::Tensor k_lens,
+                                     double softmax_scale, long wl,
+                                     long num_splits) {
+  check_q(q);
+  check_cache(k_cache, q, "k_cache");
+  check_cache(v_cache, q, "v_cache");
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
+              "fa_decode: k_cache and v_cache shapes differ");
+  TORCH_CHECK(k_cache.size(0) == q.size(0));
+  const int* klp = nullptr;
+  if (k_lens.numel() > 0) klp = check_lens(k_lens, q.size(0));
+  return run_decode<false>(q, k_cache, v_cache, klp, k_cache.size(1),
+                           nullptr, 0, softmax_scale, wl, num_splits);
+}
+
+// Paged layout: k_cache / v_cache are page pools [num_pages, page_size, hk,
+// d], block_table is int32 [b, table_width]. Shape-only checks, no host
+// sync: the table's contents are never read on the host (the kernel clamps
+// every entry it dereferences into the pool).
+std::vector<torch::Tensor> fa_decode_paged(torch::Tensor q,
+                                           torch::Tensor k_cache,
+                                           torch::Tensor v_cache,
+                                           torch::Tensor k_lens,
+                                           torch::Tensor block_table,
+                                           double softmax_scale, long wl,
+                                           long num_splits) {
+  check_q(q);
+  check_cache(k_cache, q, "k_cache");
+  check_cache(v_cache, q, "v_cache");
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
+              "fa_decode_paged: k_cache and v_cache shapes differ");
+  const long b = q.size(0);
+  const long num_pages = k_cache.size(0), ps = k_cache.size(1);
+  TORCH_CHECK(num_pages >= 1 && num_pages <= (1L << 30),
+              "fa_decode_paged: the pool needs 1..2^30 pages");
+  TORCH_CHECK(ps >= 16 && (ps & (ps - 1)) == 0,
+              "fa_decode_paged: page_size must be a power of two >= 16, got ",
+              ps);
+  TORCH_CHECK(block_table.is_cuda() &&
+                  block_table.scalar_type() == torch::kInt32 &&
+                  block_table.dim() == 2 && block_table.size(0) == b &&
+                  block_table.is_contiguous(),
+              "fa_decode_paged: block_table must be a contiguous GPU int32 "
+              "[b, table_width]");
+  const long tw = block_table.size(1);
+  TORCH_CHECK(tw >= 1 && tw * ps <= (1L << 30),
+              "fa_decode_paged: table_width * page_size must be in "
+              "[1, 2^30]");
+  const int* klp = check_lens(k_lens, b);
+  int shift = 0;
+  while ((1L << shift) < ps) ++shift;
+  return run_decode<true>(q, k_cache, v_cache, klp, tw * ps,
+                          block_table.data_ptr<int>(), shift, softmax_scale,
+                          wl, num_splits);
+}
+

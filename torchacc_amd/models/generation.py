@@ -13,13 +13,21 @@ single-query kernel that reads the cache in place through its batch and
 sequence strides (no per-step copy of the live slice), serves all q heads
 of a kv head from one read of K/V, and bounds every load by the device-side
 length, so never-written cache slots cannot reach the result. Prefill keeps
-the full-tile flash attention. A paged (block-table) KV layout is the next
-serving step; it only replaces the kernel's address computation.
+the full-tile flash attention.
+
+With ``page_size`` the caches are a ``PagedKVCache``: fixed-size pages drawn
+from one pool per layer as a sequence grows and returned when it ends, named
+by one block table that all layers share. The decode kernel's paged variant
+differs from the contiguous one in its address computation only. Not
+covered: a continuous-batching scheduler, ragged prompts, prefix-cache
+management and a paged prefill kernel (prefill attends the prompt's own
+K/V and scatters them into the pages).
 
 Usage::
 
     model = LlamaForCausalLM(llama_2_7b()).cuda().to(torch.bfloat16)
     out = model.generate(input_ids, max_new_tokens=64)   # [b, s+64]
+    out = model.generate(input_ids, max_new_tokens=64, page_size=16)
 """
 from typing import List, Optional
 
@@ -48,13 +56,161 @@ class LayerKV:
         return self.k[:, :self.len], self.v[:, :self.len]
 
 
-def _attn_with_cache(attn, x, cos, sin, cache: LayerKV, window=(-1, -1)):
+class PagedKVCache:
+    """Block-table KV cache for a whole model.
+
+    Per layer one K and one V pool [num_pages, page_size, h_kv, d]; one
+    device block table [b, table_width] (int32) shared by all layers, with a
+    host mirror; a host free list; device int32 ``lens`` [b]. Page i of the
+    table names the same physical page index in every layer's pools.
+    ``page_size`` must be a power of two (>= 16 for the HIP decode kernel).
+
+    ``reserve`` / ``free`` run on the host and copy a changed table row to
+    the device (host -> device only, no sync). Entries past a sequence's
+    reserved pages stay 0: valid indices that the decode op never
+    dereferences as long as ``lens`` stays within the reserved tokens.
+    """
+
+    def __init__(self, layer_shapes, b: int, num_pages: int, page_size: int,
+                 table_width: int, dtype, device):
+        assert page_size >= 1 and page_size & (page_size - 1) == 0, \
+            f"page_size must be a power of two, got {page_size}"
+        assert b >= 1 and num_pages >= 1 and table_width >= 1
+        self.b = b
+        self.num_pages = num_pages
+        self.page_size = page_size
+        self.shift = page_size.bit_length() - 1
+        self.table_width = table_width
+        self.k = [torch.empty(num_pages, page_size, hk, d, dtype=dtype,
+                              device=device) for hk, d in layer_shapes]
+        self.v = [torch.empty_like(k) for k in self.k]
+        self.table_host = torch.zeros(b, table_width, dtype=torch.int32)
+        self.table = torch.zeros(b, table_width, dtype=torch.int32,
+                                 device=device)
+        self.lens = torch.zeros(b, dtype=torch.int32, device=device)
+        self.free_pages = list(range(num_pages - 1, -1, -1))  # pop() -> 0..
+        self.owned = [0] * b       # pages held per sequence
+        self.len = 0               # host length (all sequences alike)
+        self._slots = None         # flat slots of the step being written
+        self._layers = [_PagedLayer(self, i) for i in range(len(self.k))]
+
+    @classmethod
+    def for_model(cls, model, b: int, num_pages: int, page_size: int,
+                  max_len: int):
+        p = next(model.parameters())
+        shapes = [(layer.self_attn.num_kv_heads, layer.self_attn.head_dim)
+                  for layer in model.layers]
+        width = (max_len + page_size - 1) // page_size
+        return cls(shapes, b, num_pages, page_size, width, p.dtype, p.device)
+
+    def __iter__(self):
+        return iter(self._layers)
+
+    def reserve(self, seq: int, n_tokens: int):
+        """Grow sequence ``seq`` until it holds ``n_tokens`` slots."""
+        need = (n_tokens + self.page_size - 1) // self.page_size
+        have = self.owned[seq]
+        if need <= have:
+            return
+        if need > self.table_width:
+            raise RuntimeError(
+                f"PagedKVCache: {n_tokens} tokens need {need} pages, the "
+                f"block table holds {self.table_width} per sequence")
+        if need - have > len(self.free_pages):
+            raise RuntimeError(
+                f"PagedKVCache: pool exhausted: sequence {seq} needs "
+                f"{need - have} more pages of {self.page_size} tokens for "
+                f"{n_tokens} tokens, {len(self.free_pages)} of "
+                f"{self.num_pages} are free")
+        for i in range(have, need):
+            self.table_host[seq, i] = self.free_pages.pop()
+        self.owned[seq] = need
+        self.table[seq].copy_(self.table_host[seq])
+
+    def free(self, seq: int):
+        """Return every page of sequence ``seq`` to the pool."""
+        n = self.owned[seq]
+        if n == 0:
+            return
+        self.free_pages.extend(reversed(self.table_host[seq, :n].tolist()))
+        self.table_host[seq, :n] = 0
+        self.owned[seq] = 0
+        self.table[seq].copy_(self.table_host[seq])
+
+    def slot_indices(self, positions: torch.Tensor) -> torch.Tensor:
+        """Token positions [b, s] (device, int64) -> flat slot indices
+        [b * s] into a pool viewed as [num_pages * page_size, h_kv, d]:
+        table[seq, pos >> shift] * page_size + (pos & mask). Pure device
+        arithmetic on the device table, so it captures into a graph."""
+        page = self.table.gather(1, (positions >> self.shift)).long()
+        return (page * self.page_size
+                + (positions & (self.page_size - 1))).reshape(-1)
+
+    def begin_step(self, positions: torch.Tensor):
+        """Compute the slots the step's tokens are written to, once for all
+        layers."""
+        self._slots = self.slot_indices(positions)
+
+    def gather(self, layer: int, n_tokens: int):
+        """Contiguous copy [b, n_tokens, h_kv, d] of a layer's K and V."""
+        pages = (n_tokens + self.page_size - 1) // self.page_size
+        idx = self.table[:, :pages].reshape(-1).long()
+        out = []
+        for pool in (self.k[layer], self.v[layer]):
+            t = pool.index_select(0, idx)
+            out.append(t.view(self.b, pages * self.page_size,
+                              *pool.shape[2:])[:, :n_tokens])
+        return out
+
+
+class _PagedLayer:
+    """One layer of a PagedKVCache, as _attn_with_cache sees it."""
+
+    def __init__(self, owner: PagedKVCache, index: int):
+        self.owner = owner
+        self.index = index
+        self.k = owner.k[index]
+        self.v = owner.v[index]
+
+    @property
+    def len(self):
+        return self.owner.len
+
+    def write(self, k: torch.Tensor, v: torch.Tensor):
+        slots = self.owner._slots
+        for pool, new in ((self.k, k), (self.v, v)):
+            pool.view(-1, *pool.shape[2:]).index_copy_(
+                0, slots, new.reshape(-1, *new.shape[2:]))
+
+
+def _attn_paged(q, k, v, cache: _PagedLayer, window):
+    pc = cache.owner
+    s = q.shape[1]
+    cache.write(k, v)
+    if s == 1:
+        return flash_attn_with_kvcache(
+            q, cache.k, cache.v, cache_seqlens=pc.lens,
+            window_size=(window[0], -1), block_table=pc.table)
+    if pc.len == 0:
+        # prefill: the prompt attends its own freshly computed K/V
+        return flash_attn_xla(q, k, v, causal=True, window_size=window)
+    # several new tokens against a non-empty paged cache (generate never
+    # does this): there is no paged prefill kernel, so gather the live pages
+    # into a contiguous copy
+    kc, vc = pc.gather(cache.index, pc.len + s)
+    return flash_attn_xla(q, kc, vc, causal=True, window_size=window)
+
+
+def _attn_with_cache(attn, x, cos, sin, cache, window=(-1, -1)):
     b, s, _ = x.shape
     h, hk = attn.num_heads, attn.num_kv_heads
     q = attn.q_proj(x).view(b, s, h, attn.head_dim)
     k = attn.k_proj(x).view(b, s, hk, attn.head_dim)
     v = attn.v_proj(x).view(b, s, hk, attn.head_dim)
     q, k = apply_rotary_pos_emb(q, k, cos, sin)
+    if isinstance(cache, _PagedLayer):
+        o = _attn_paged(q, k, v, cache, window)
+        return attn.o_proj(o.reshape(b, s, h * attn.head_dim))
     cache.append(k, v)
     kc, vc = cache.view()
     if s == 1:
@@ -67,11 +223,18 @@ def _attn_with_cache(attn, x, cos, sin, cache: LayerKV, window=(-1, -1)):
     return attn.o_proj(o.reshape(b, s, h * attn.head_dim))
 
 
-def _forward_step(model, ids: torch.Tensor, caches: List[LayerKV],
-                  pos: int) -> torch.Tensor:
+def _forward_step(model, ids: torch.Tensor, caches, pos: int) -> torch.Tensor:
     """Run [b, s] new tokens at absolute positions [pos, pos+s) through the
-    model with caches; returns last-position logits [b, vocab]."""
-    s = ids.shape[1]
+    model with caches (a list of LayerKV or one PagedKVCache, whose pages
+    for pos+s tokens are already reserved); returns last-position logits
+    [b, vocab]."""
+    b, s = ids.shape
+    paged = isinstance(caches, PagedKVCache)
+    if paged:
+        # slots once per step, not per layer; the host knows the length
+        caches.begin_step(torch.arange(pos, pos + s, device=ids.device)
+                          .expand(b, s))
+        caches.lens.fill_(pos + s)
     cos = model.rope_cos[pos:pos + s]
     sin = model.rope_sin[pos:pos + s]
     delta = model.embed_tokens(ids)
@@ -93,14 +256,24 @@ def _forward_step(model, ids: torch.Tensor, caches: List[LayerKV],
         residual = resid2
     x, _ = fused_add_rms_norm(delta, residual, model.norm.weight,
                               model.norm.variance_epsilon)
+    if paged:
+        caches.len = pos + s
     return model.lm_head(x[:, -1:]).squeeze(1)
 
 
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              temperature: float = 0.0, top_k: int = 0,
-             eos_token_id: Optional[int] = None) -> torch.Tensor:
-    """Greedy (temperature=0) or sampled decode; returns [b, s + new]."""
+             eos_token_id: Optional[int] = None,
+             page_size: Optional[int] = None,
+             kv_pool: Optional[PagedKVCache] = None) -> torch.Tensor:
+    """Greedy (temperature=0) or sampled decode; returns [b, s + new].
+
+    ``page_size`` selects the paged KV cache: pages are reserved on demand
+    as the length grows and the decode steps read them through the block
+    table. ``kv_pool`` is a caller-owned PagedKVCache to draw the pages from
+    instead of a fresh pool (its page size is used; batch and table width
+    must fit); the call's pages go back to it on return."""
     assert input_ids.dim() == 2
     b, s0 = input_ids.shape
     cfg = model.config
@@ -108,14 +281,46 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     assert max_len <= cfg.max_position_embeddings, \
         (f"{max_len} tokens exceed max_position_embeddings="
          f"{cfg.max_position_embeddings}")
+    if page_size is not None or kv_pool is not None:
+        pool = kv_pool
+        if pool is None:
+            pages = (max_len + page_size - 1) // page_size
+            pool = PagedKVCache.for_model(model, b, b * pages, page_size,
+                                          max_len)
+        assert pool.b == b, \
+            f"kv_pool serves {pool.b} sequences, the prompt has {b}"
+        assert all(n == 0 for n in pool.owned[:b]), \
+            "kv_pool sequences are still in use"
+        pool.len = 0
+        try:
+            return _generate_loop(model, input_ids, max_new_tokens,
+                                  temperature, top_k, eos_token_id, pool)
+        finally:
+            for i in range(b):
+                pool.free(i)
     p = next(model.parameters())
     caches = [
         LayerKV(b, max_len, layer.self_attn.num_kv_heads,
                 layer.self_attn.head_dim, p.dtype, p.device)
         for layer in model.layers
     ]
+    return _generate_loop(model, input_ids, max_new_tokens, temperature,
+                          top_k, eos_token_id, caches)
+
+
+def _step(model, ids, caches, pos: int) -> torch.Tensor:
+    """_forward_step, reserving the pages of a paged cache first."""
+    if isinstance(caches, PagedKVCache):
+        for i in range(ids.shape[0]):
+            caches.reserve(i, pos + ids.shape[1])
+    return _forward_step(model, ids, caches, pos)
+
+
+def _generate_loop(model, input_ids, max_new_tokens, temperature, top_k,
+                   eos_token_id, caches) -> torch.Tensor:
+    b = input_ids.shape[0]
     out = input_ids
-    logits = _forward_step(model, input_ids, caches, 0)
+    logits = _step(model, input_ids, caches, 0)
     finished = torch.zeros(b, dtype=torch.bool, device=input_ids.device)
     for i in range(max_new_tokens):
         if temperature > 0.0:
@@ -135,7 +340,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
         if eos_token_id is not None and bool(finished.all()):
             break
         if i + 1 < max_new_tokens:
-            logits = _forward_step(model, nxt, caches, out.shape[1] - 1)
+            logits = _step(model, nxt, caches, out.shape[1] - 1)
     return out
 
 
@@ -153,23 +358,41 @@ class GraphDecoder:
     buffer inside the graph. Replaying the graph N times decodes N tokens
     with no host work in the loop (greedy only; sampling/eos use the eager
     path).
+
+    With ``page_size`` the caches are one ``PagedKVCache`` (``self.paged``)
+    with ceil(max_len / page_size) pages reserved per sequence up front; the
+    captured step computes its write slots from the device block table and
+    runs the paged decode op. The table and the lengths are device buffers
+    read at replay, so a later ``decode`` may run with another page
+    assignment (free and re-reserve in another order) without recapture.
     """
 
-    def __init__(self, model, b: int, max_len: int):
+    def __init__(self, model, b: int, max_len: int,
+                 page_size: Optional[int] = None):
         p = next(model.parameters())
         assert p.is_cuda, "GraphDecoder requires a GPU model"
         self.model = model
         self.max_len = max_len
         d = model.layers[0].self_attn.head_dim
-        self.caches = [
-            LayerKV(b, max_len, layer.self_attn.num_kv_heads, d, p.dtype,
-                    p.device)
-            for layer in model.layers
-        ]
         dev = p.device
+        self.paged = None
+        if page_size is None:
+            self.caches = [
+                LayerKV(b, max_len, layer.self_attn.num_kv_heads, d, p.dtype,
+                        p.device)
+                for layer in model.layers
+            ]
+            self.k_lens = torch.zeros(b, dtype=torch.int32, device=dev)
+        else:
+            pages = (max_len + page_size - 1) // page_size
+            self.paged = PagedKVCache.for_model(model, b, b * pages,
+                                                page_size, max_len)
+            for i in range(b):
+                self.paged.reserve(i, max_len)
+            self.caches = self.paged
+            self.k_lens = self.paged.lens
         self.ids = torch.zeros(b, 1, dtype=torch.long, device=dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)
-        self.k_lens = torch.zeros(b, dtype=torch.int32, device=dev)
         self.graph = None
 
     def _step_static(self):
@@ -179,6 +402,9 @@ class GraphDecoder:
         delta = m.embed_tokens(self.ids)
         residual = None
         b, s = self.ids.shape
+        if self.paged is not None:
+            # in-graph slot computation, once per step for all layers
+            self.paged.begin_step(self.pos.expand(b, 1))
         for layer, cache in zip(m.layers, self.caches):
             y1, resid = fused_add_rms_norm(
                 delta, residual, layer.input_layernorm.weight,
@@ -189,11 +415,18 @@ class GraphDecoder:
             k = attn.k_proj(y1).view(b, s, hk, attn.head_dim)
             v = attn.v_proj(y1).view(b, s, hk, attn.head_dim)
             q, k = apply_rotary_pos_emb(q, k, cos, sin)
-            cache.k.index_copy_(1, self.pos, k)
-            cache.v.index_copy_(1, self.pos, v)
-            o = flash_attn_with_kvcache(
-                q, cache.k, cache.v, cache_seqlens=self.k_lens,
-                softmax_scale=attn.head_dim ** -0.5)
+            if self.paged is not None:
+                cache.write(k, v)
+                o = flash_attn_with_kvcache(
+                    q, cache.k, cache.v, cache_seqlens=self.k_lens,
+                    softmax_scale=attn.head_dim ** -0.5,
+                    block_table=self.paged.table)
+            else:
+                cache.k.index_copy_(1, self.pos, k)
+                cache.v.index_copy_(1, self.pos, v)
+                o = flash_attn_with_kvcache(
+                    q, cache.k, cache.v, cache_seqlens=self.k_lens,
+                    softmax_scale=attn.head_dim ** -0.5)
             a = attn.o_proj(o.reshape(b, s, h * attn.head_dim))
             y2, resid2 = fused_add_rms_norm(
                 a, resid, layer.post_attention_layernorm.weight,
@@ -214,12 +447,18 @@ class GraphDecoder:
     def decode(self, prompt_ids: torch.Tensor, max_new_tokens: int):
         b, s0 = prompt_ids.shape
         assert s0 + max_new_tokens <= self.max_len
-        for c in self.caches:
-            c.len = 0
+        if self.paged is not None:
+            for i in range(b):      # no-op unless the caller freed pages
+                self.paged.reserve(i, self.max_len)
+            self.paged.len = 0
+        else:
+            for c in self.caches:
+                c.len = 0
         # prefill eagerly (dynamic shapes), fill the static caches
         logits = _forward_step(self.model, prompt_ids, self.caches, 0)
-        for c in self.caches:
-            c.len = self.max_len  # cache buffers are written in place now
+        if self.paged is None:
+            for c in self.caches:
+                c.len = self.max_len  # cache buffers are written in place now
         first = logits.argmax(-1, keepdim=True)
         tokens = [first]
         if max_new_tokens == 1:

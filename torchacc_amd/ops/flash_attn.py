@@ -732,9 +732,65 @@ def _decode_fallback_gpu(q, k_cache, v_cache, lens, softmax_scale, wl):
     return out, lse
 
 
+def _gather_pages(pool, block_table):
+    """Page pool [num_pages, page_size, hk, d] and table [b, w] -> the
+    contiguous cache [b, w * page_size, hk, d] the table describes. Entries
+    are clamped into the pool as the kernel clamps them, so the entries of
+    unused logical pages cannot make the gather raise."""
+    n, ps, hk, d = pool.shape
+    b, w = block_table.shape
+    idx = block_table.reshape(-1).long().clamp(0, n - 1)
+    return pool.index_select(0, idx).view(b, w * ps, hk, d)
+
+
+def _paged_kernel_page_size(ps: int) -> bool:
+    return ps >= 16 and (ps & (ps - 1)) == 0
+
+
+def _decode_paged(q, k_pool, v_pool, lens, block_table, softmax_scale, wl,
+                  num_splits):
+    """flash_attn_with_kvcache with a block table; returns (out, lse)."""
+    assert lens is not None, \
+        "flash_attn_with_kvcache: block_table requires cache_seqlens"
+    assert block_table.dim() == 2 and block_table.shape[0] == q.shape[0], \
+        (f"block_table must be [batch, table_width], got "
+         f"{tuple(block_table.shape)} for batch {q.shape[0]}")
+    assert block_table.dtype in (torch.int32, torch.int64), \
+        "block_table must be int32 or int64"
+    assert block_table.device == q.device, \
+        "block_table must live on the device of q"
+    assert block_table.shape[1] >= 1 and k_pool.shape[0] >= 1
+    assert q.shape[3] == k_pool.shape[3]
+    if block_table.dtype != torch.int32:
+        block_table = block_table.to(torch.int32)   # device-side, no sync
+    ps = k_pool.shape[1]
+
+    ext = dispatch(q)
+    if ext is None:
+        return _ref_decode(q, _gather_pages(k_pool, block_table),
+                           _gather_pages(v_pool, block_table), lens,
+                           softmax_scale, wl)
+    if (q.dtype in (torch.float16, torch.bfloat16)
+            and q.shape[-1] in (64, 128) and _paged_kernel_page_size(ps)):
+        return ext.fa_decode_paged(
+            q.contiguous(), k_pool, v_pool, lens.contiguous(),
+            block_table.contiguous(), softmax_scale, wl, num_splits)
+    key = ("paged", q.dtype, q.shape[-1], ps)
+    if key not in _warned_decode:
+        _warned_decode.add(key)
+        from ..utils.logger import logger
+        logger.warning(
+            "flash_attn_with_kvcache: dtype %s / head_dim %d / page_size %d "
+            "is not covered by the paged decode kernel; gathering the pages "
+            "into a contiguous copy on the device", *key[1:])
+    return _decode_fallback_gpu(q, _gather_pages(k_pool, block_table),
+                                _gather_pages(v_pool, block_table), lens,
+                                softmax_scale, wl)
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
                             softmax_scale=None, window_size=(-1, -1),
-                            num_splits=0, return_lse=False):
+                            num_splits=0, return_lse=False, block_table=None):
     """Single-query (decode) attention over a KV cache, inference only.
 
     q [b, 1, hq, d]; k_cache / v_cache [b, cap, hk, d] with hk | hq, read in
@@ -755,6 +811,21 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
     which reads the lengths on the host and cannot be graph-captured.
     Returns out [b, 1, hq, d], and lse [b, hq, 1] (fp32, natural log) with
     ``return_lse``.
+
+    Paged layout: with ``block_table`` (int32/int64 [b, table_width], same
+    device) the caches are page pools [num_pages, page_size, hk, d] (page
+    and slot strides arbitrary, [hk, d] dense) and ``cache_seqlens`` is
+    required. Key j of sequence i lies in page ``block_table[i, j //
+    page_size]`` at slot ``j % page_size``; cap = table_width * page_size.
+    Entries for logical pages < ceil(len_i / page_size) must be valid page
+    indices; all other entries are never dereferenced, and the slots they
+    would name are never loaded. Pages may be shared between sequences. The
+    kernel clamps every page index it reads into [0, num_pages - 1], so a
+    bad entry gives wrong numbers, never an out-of-bounds read. A page size
+    that is a power of two >= 16 runs the paged HIP kernel, whose result is
+    bitwise the contiguous kernel's on the gathered cache at the same
+    ``num_splits``; other page sizes (and the dtypes / head dims named
+    above) gather the pages into a contiguous copy on the device first.
     """
     assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
         "expected q [b, 1, hq, d] and caches [b, cap, hk, d]"
@@ -764,7 +835,8 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
     assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
     assert q.device == k_cache.device == v_cache.device
     assert k_cache.shape == v_cache.shape
-    assert q.shape[0] == k_cache.shape[0] and q.shape[3] == k_cache.shape[3]
+    assert block_table is not None or q.shape[0] == k_cache.shape[0]
+    assert q.shape[3] == k_cache.shape[3]
     assert q.shape[2] % k_cache.shape[2] == 0, "GQA requires h_k | h_q"
     if torch.is_grad_enabled() and any(
             t.requires_grad for t in (q, k_cache, v_cache)):
@@ -783,7 +855,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
     wl = int(window_size[0])
 
     ext = dispatch(q)
-    if ext is None:
+    if block_table is not None:
+        out, lse = _decode_paged(q, k_cache, v_cache, lens, block_table,
+                                 softmax_scale, wl, num_splits)
+    elif ext is None:
         out, lse = _ref_decode(q, k_cache, v_cache, lens, softmax_scale, wl)
     elif (q.dtype in (torch.float16, torch.bfloat16)
           and q.shape[-1] in (64, 128)):
