@@ -25,6 +25,8 @@ def main():
     p.add_argument("--warmup", type=int, default=8)
     p.add_argument("--graph", action="store_true",
                    help="hipGraph-captured decode step (greedy)")
+    p.add_argument("--kv-dtype", default=None, choices=["fp8"],
+                   help="KV cache storage (default: the model dtype)")
     args = p.parse_args()
 
     from torchacc_amd.models import (LlamaForCausalLM, llama_2_7b,
@@ -47,17 +49,20 @@ def main():
     if args.graph:
         from torchacc_amd.models.generation import GraphDecoder
         dec = GraphDecoder(model, args.batch,
-                           args.prompt + args.new + args.warmup + 2)
+                           args.prompt + args.new + args.warmup + 2,
+                           kv_dtype=args.kv_dtype)
         dec.decode(ids, args.warmup)  # warm + capture
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         out = dec.decode(ids, args.new)
     else:
-        model.generate(ids, max_new_tokens=args.warmup)  # warm
+        model.generate(ids, max_new_tokens=args.warmup,
+                       kv_dtype=args.kv_dtype)  # warm
         if on_gpu:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = model.generate(ids, max_new_tokens=args.new)
+        out = model.generate(ids, max_new_tokens=args.new,
+                             kv_dtype=args.kv_dtype)
     if on_gpu:
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -70,6 +75,7 @@ def main():
         "prompt": args.prompt, "new": args.new,
         "dtype": "bf16" if on_gpu else "fp32",
         "graph": args.graph,
+        "kv_dtype": args.kv_dtype or ("bf16" if on_gpu else "fp32"),
     }))
 
 

@@ -79,6 +79,24 @@ std::vector<torch::Tensor> fa_decode_paged(torch::Tensor q,
                                            torch::Tensor block_table,
                                            double softmax_scale, long wl,
                                            long num_splits);
+std::vector<torch::Tensor> fa_decode_fp8(torch::Tensor q,
+                                         torch::Tensor k_cache,
+                                         torch::Tensor v_cache,
+                                         torch::Tensor k_lens,
+                                         torch::Tensor k_scale,
+                                         torch::Tensor v_scale,
+                                         double softmax_scale, long wl,
+                                         long num_splits);
+std::vector<torch::Tensor> fa_decode_paged_fp8(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_lens, torch::Tensor block_table, torch::Tensor k_scale,
+    torch::Tensor v_scale, double softmax_scale, long wl, long num_splits);
+
+// kv_cache_write.hip
+void kv_cache_write_fp8(torch::Tensor k, torch::Tensor v,
+                        torch::Tensor k_cache, torch::Tensor v_cache,
+                        torch::Tensor slots, torch::Tensor k_scale,
+                        torch::Tensor v_scale);
 
 // gemm.hip (hipBLASLt tuned GEMM)
 std::vector<int64_t> lt_gemm_candidates(int64_t m, int64_t n, int64_t k,
@@ -108,6 +126,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_varlen_backward", &fa_varlen_backward);
   m.def("fa_decode", &fa_decode);
   m.def("fa_decode_paged", &fa_decode_paged);
+  m.def("fa_decode_fp8", &fa_decode_fp8);
+  m.def("fa_decode_paged_fp8", &fa_decode_paged_fp8);
+  m.def("kv_cache_write_fp8", &kv_cache_write_fp8);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);
   m.def("lt_gemm", &lt_gemm, pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("ta"), pybind11::arg("tb"),

@@ -23,34 +23,126 @@ covered: a continuous-batching scheduler, ragged prompts, prefix-cache
 management and a paged prefill kernel (prefill attends the prompt's own
 K/V and scatters them into the pages).
 
+With ``kv_dtype="fp8"`` either cache stores OCP e4m3fn codes (one byte per
+element, half the pool and half the bytes a decode step reads) with one fp32
+scale per layer and kv head for K and for V. New rows are quantised by
+``kv_cache_write_fp8`` (one launch for K and V) and the decode kernel's fp8
+variant converts them back in registers; prefill still attends the prompt's
+own unquantised K/V. The scales are set from the prompt at prefill (amax *
+headroom / 448, on the device, no host sync) or given by the caller
+(``kv_scales``); later tokens outside the range saturate at +-448 * scale.
+
 Usage::
 
     model = LlamaForCausalLM(llama_2_7b()).cuda().to(torch.bfloat16)
     out = model.generate(input_ids, max_new_tokens=64)   # [b, s+64]
     out = model.generate(input_ids, max_new_tokens=64, page_size=16)
+    out = model.generate(input_ids, max_new_tokens=64, kv_dtype="fp8")
 """
 from typing import List, Optional
 
 import torch
 
-from ..ops.flash_attn import flash_attn_with_kvcache, flash_attn_xla
+from ..ops.flash_attn import (FP8_DTYPE, FP8_MAX, dequantize_kv_fp8,
+                              flash_attn_with_kvcache, flash_attn_xla,
+                              kv_cache_write_fp8)
 from ..ops.rmsnorm import fused_add_rms_norm
 from ..ops.rope import apply_rotary_pos_emb
 
 
-class LayerKV:
-    """Preallocated per-layer cache: k/v [b, max_len, h_kv, d]."""
+# smallest scale the prefill calibration writes: keeps 1 / scale finite when
+# a head's prompt K or V is all zero
+KV_SCALE_FLOOR = 2.0 ** -20
 
-    def __init__(self, b: int, max_len: int, hk: int, d: int, dtype, device):
-        self.k = torch.empty(b, max_len, hk, d, dtype=dtype, device=device)
-        self.v = torch.empty(b, max_len, hk, d, dtype=dtype, device=device)
+
+def _is_fp8(kv_dtype) -> bool:
+    """None -> the model dtype; "fp8" (or torch.float8_e4m3fn) -> e4m3."""
+    if kv_dtype is None:
+        return False
+    if kv_dtype in ("fp8", "fp8_e4m3", FP8_DTYPE):
+        return True
+    raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+
+
+def _new_scale(hk: int, device) -> torch.Tensor:
+    return torch.ones(hk, dtype=torch.float32, device=device)
+
+
+def _calibrate_scales(cache, k: torch.Tensor, v: torch.Tensor):
+    """Prefill of an fp8 cache: scale[h] = max(amax_h * headroom / 448,
+    floor) from the prompt's post-RoPE K and its V, written in place into
+    the cache's scale buffers on the device (no host sync). ``headroom`` is
+    None when the caller supplied the scales."""
+    if cache.headroom is None:
+        return
+    for buf, x in ((cache.k_scale, k), (cache.v_scale, v)):
+        amax = x.float().abs().amax(dim=(0, 1, 3))
+        buf.copy_((amax * (cache.headroom / FP8_MAX))
+                  .clamp_min(KV_SCALE_FLOOR))
+
+
+def _configure_scales(caches, kv_scales, headroom: float):
+    """Per-call scale policy of fp8 caches (a list of LayerKV or one
+    PagedKVCache): given scales are copied into the buffers and prefill
+    leaves them alone, otherwise prefill calibrates with ``headroom``."""
+    layers = list(caches)
+    if kv_scales is None:
+        assert headroom > 0.0, "kv_scale_headroom must be positive"
+        for c in layers:
+            c.headroom = float(headroom)
+        return
+    assert len(kv_scales) == len(layers), \
+        f"kv_scales needs one (k_scale, v_scale) per layer ({len(layers)})"
+    for c, (ks, vs) in zip(layers, kv_scales):
+        for buf, val in ((c.k_scale, ks), (c.v_scale, vs)):
+            buf.copy_(torch.as_tensor(val, dtype=torch.float32)
+                      .expand_as(buf))
+        c.headroom = None
+
+
+class LayerKV:
+    """Preallocated per-layer cache: k/v [b, max_len, h_kv, d].
+
+    ``kv_dtype="fp8"``: float8_e4m3fn storage plus ``k_scale`` / ``v_scale``
+    (fp32 [h_kv] device buffers, 1 until set); rows are written by
+    ``kv_cache_write_fp8`` at slots batch * max_len + position, computed on
+    the device."""
+
+    def __init__(self, b: int, max_len: int, hk: int, d: int, dtype, device,
+                 kv_dtype=None):
+        self.fp8 = _is_fp8(kv_dtype)
+        store = FP8_DTYPE if self.fp8 else dtype
+        self.k = torch.empty(b, max_len, hk, d, dtype=store, device=device)
+        self.v = torch.empty(b, max_len, hk, d, dtype=store, device=device)
         self.len = 0
+        if self.fp8:
+            self.k_scale = _new_scale(hk, device)
+            self.v_scale = _new_scale(hk, device)
+            self.headroom = 2.0
+            self._base = (torch.arange(b, device=device) * max_len).view(b, 1)
 
     def append(self, k: torch.Tensor, v: torch.Tensor):
         s = k.shape[1]
-        self.k[:, self.len:self.len + s] = k
-        self.v[:, self.len:self.len + s] = v
+        if self.fp8:
+            self.write_at(k, v, torch.arange(self.len, self.len + s,
+                                             device=k.device))
+        else:
+            self.k[:, self.len:self.len + s] = k
+            self.v[:, self.len:self.len + s] = v
         self.len += s
+
+    def write_at(self, k: torch.Tensor, v: torch.Tensor, pos: torch.Tensor):
+        """fp8 only: quantise k / v [b, s, h_kv, d] into positions ``pos``
+        (int64 [s], device) of every sequence."""
+        slots = (self._base + pos.view(1, -1)).reshape(-1)
+        kv_cache_write_fp8(k, v, self.k, self.v, slots, self.k_scale,
+                           self.v_scale)
+
+    def scales(self) -> dict:
+        """Keyword arguments of the decode op for this cache."""
+        if not self.fp8:
+            return {}
+        return {"k_scale": self.k_scale, "v_scale": self.v_scale}
 
     def view(self):
         return self.k[:, :self.len], self.v[:, :self.len]
@@ -69,10 +161,13 @@ class PagedKVCache:
     the device (host -> device only, no sync). Entries past a sequence's
     reserved pages stay 0: valid indices that the decode op never
     dereferences as long as ``lens`` stays within the reserved tokens.
+
+    ``kv_dtype="fp8"``: the pools are float8_e4m3fn and every layer owns a
+    ``k_scale`` and a ``v_scale`` (fp32 [h_kv] device buffers, 1 until set).
     """
 
     def __init__(self, layer_shapes, b: int, num_pages: int, page_size: int,
-                 table_width: int, dtype, device):
+                 table_width: int, dtype, device, kv_dtype=None):
         assert page_size >= 1 and page_size & (page_size - 1) == 0, \
             f"page_size must be a power of two, got {page_size}"
         assert b >= 1 and num_pages >= 1 and table_width >= 1
@@ -81,9 +176,14 @@ class PagedKVCache:
         self.page_size = page_size
         self.shift = page_size.bit_length() - 1
         self.table_width = table_width
-        self.k = [torch.empty(num_pages, page_size, hk, d, dtype=dtype,
+        self.fp8 = _is_fp8(kv_dtype)
+        store = FP8_DTYPE if self.fp8 else dtype
+        self.k = [torch.empty(num_pages, page_size, hk, d, dtype=store,
                               device=device) for hk, d in layer_shapes]
         self.v = [torch.empty_like(k) for k in self.k]
+        if self.fp8:
+            self.k_scale = [_new_scale(hk, device) for hk, _ in layer_shapes]
+            self.v_scale = [_new_scale(hk, device) for hk, _ in layer_shapes]
         self.table_host = torch.zeros(b, table_width, dtype=torch.int32)
         self.table = torch.zeros(b, table_width, dtype=torch.int32,
                                  device=device)
@@ -96,12 +196,13 @@ class PagedKVCache:
 
     @classmethod
     def for_model(cls, model, b: int, num_pages: int, page_size: int,
-                  max_len: int):
+                  max_len: int, kv_dtype=None):
         p = next(model.parameters())
         shapes = [(layer.self_attn.num_kv_heads, layer.self_attn.head_dim)
                   for layer in model.layers]
         width = (max_len + page_size - 1) // page_size
-        return cls(shapes, b, num_pages, page_size, width, p.dtype, p.device)
+        return cls(shapes, b, num_pages, page_size, width, p.dtype, p.device,
+                   kv_dtype=kv_dtype)
 
     def __iter__(self):
         return iter(self._layers)
@@ -157,7 +258,10 @@ class PagedKVCache:
         idx = self.table[:, :pages].reshape(-1).long()
         out = []
         for pool in (self.k[layer], self.v[layer]):
-            t = pool.index_select(0, idx)
+            if self.fp8:   # float8 has no index kernels: move the bytes
+                t = pool.view(torch.uint8).index_select(0, idx).view(FP8_DTYPE)
+            else:
+                t = pool.index_select(0, idx)
             out.append(t.view(self.b, pages * self.page_size,
                               *pool.shape[2:])[:, :n_tokens])
         return out
@@ -171,13 +275,27 @@ class _PagedLayer:
         self.index = index
         self.k = owner.k[index]
         self.v = owner.v[index]
+        self.fp8 = owner.fp8
+        self.headroom = 2.0
+        if self.fp8:
+            self.k_scale = owner.k_scale[index]
+            self.v_scale = owner.v_scale[index]
 
     @property
     def len(self):
         return self.owner.len
 
+    def scales(self) -> dict:
+        if not self.fp8:
+            return {}
+        return {"k_scale": self.k_scale, "v_scale": self.v_scale}
+
     def write(self, k: torch.Tensor, v: torch.Tensor):
         slots = self.owner._slots
+        if self.fp8:
+            kv_cache_write_fp8(k, v, self.k, self.v, slots, self.k_scale,
+                               self.v_scale)
+            return
         for pool, new in ((self.k, k), (self.v, v)):
             pool.view(-1, *pool.shape[2:]).index_copy_(
                 0, slots, new.reshape(-1, *new.shape[2:]))
@@ -186,11 +304,14 @@ class _PagedLayer:
 def _attn_paged(q, k, v, cache: _PagedLayer, window):
     pc = cache.owner
     s = q.shape[1]
+    if cache.fp8 and pc.len == 0:
+        _calibrate_scales(cache, k, v)
     cache.write(k, v)
     if s == 1:
         return flash_attn_with_kvcache(
             q, cache.k, cache.v, cache_seqlens=pc.lens,
-            window_size=(window[0], -1), block_table=pc.table)
+            window_size=(window[0], -1), block_table=pc.table,
+            **cache.scales())
     if pc.len == 0:
         # prefill: the prompt attends its own freshly computed K/V
         return flash_attn_xla(q, k, v, causal=True, window_size=window)
@@ -198,6 +319,9 @@ def _attn_paged(q, k, v, cache: _PagedLayer, window):
     # does this): there is no paged prefill kernel, so gather the live pages
     # into a contiguous copy
     kc, vc = pc.gather(cache.index, pc.len + s)
+    if cache.fp8:
+        kc = dequantize_kv_fp8(kc, cache.k_scale, q.dtype)
+        vc = dequantize_kv_fp8(vc, cache.v_scale, q.dtype)
     return flash_attn_xla(q, kc, vc, causal=True, window_size=window)
 
 
@@ -211,11 +335,23 @@ def _attn_with_cache(attn, x, cos, sin, cache, window=(-1, -1)):
     if isinstance(cache, _PagedLayer):
         o = _attn_paged(q, k, v, cache, window)
         return attn.o_proj(o.reshape(b, s, h * attn.head_dim))
+    fresh = cache.len == 0
+    if cache.fp8 and fresh:
+        _calibrate_scales(cache, k, v)
     cache.append(k, v)
     kc, vc = cache.view()
     if s == 1:
         # decode: the strided view is read in place, no copy
-        o = flash_attn_with_kvcache(q, kc, vc, window_size=(window[0], -1))
+        o = flash_attn_with_kvcache(q, kc, vc, window_size=(window[0], -1),
+                                    **cache.scales())
+    elif cache.fp8:
+        if not fresh:
+            # several new tokens against a non-empty fp8 cache (generate
+            # never does this): attend a dequantised copy
+            k = dequantize_kv_fp8(kc, cache.k_scale, q.dtype)
+            v = dequantize_kv_fp8(vc, cache.v_scale, q.dtype)
+        # prefill: the prompt attends its own unquantised K/V
+        o = flash_attn_xla(q, k, v, causal=True, window_size=window)
     else:
         # bottom-right causal: the s new queries attend all cached keys up
         # to their own position
@@ -266,14 +402,28 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              temperature: float = 0.0, top_k: int = 0,
              eos_token_id: Optional[int] = None,
              page_size: Optional[int] = None,
-             kv_pool: Optional[PagedKVCache] = None) -> torch.Tensor:
+             kv_pool: Optional[PagedKVCache] = None,
+             kv_dtype=None, kv_scales=None,
+             kv_scale_headroom: float = 2.0) -> torch.Tensor:
     """Greedy (temperature=0) or sampled decode; returns [b, s + new].
 
     ``page_size`` selects the paged KV cache: pages are reserved on demand
     as the length grows and the decode steps read them through the block
     table. ``kv_pool`` is a caller-owned PagedKVCache to draw the pages from
     instead of a fresh pool (its page size is used; batch and table width
-    must fit); the call's pages go back to it on return."""
+    must fit); the call's pages go back to it on return.
+
+    ``kv_dtype="fp8"`` stores K and V as float8_e4m3fn codes with one fp32
+    scale per layer and kv head (contiguous or paged alike). A caller-owned
+    ``kv_pool`` decides the dtype itself; a conflicting ``kv_dtype`` raises.
+    At prefill the scales become max(amax * kv_scale_headroom / 448, floor),
+    amax taken per kv head over the prompt's post-RoPE K and over its V, on
+    the device and without a host sync; tokens decoded later that exceed
+    448 * scale saturate. The default headroom of 2 is a design choice (one
+    binade of room for later tokens at the cost of one bit of resolution),
+    not the outcome of a measurement. ``kv_scales``, a list with one
+    ``(k_scale, v_scale)`` per layer (tensors [h_kv] or scalars), replaces
+    the calibration, e.g. for checkpoints that ship calibrated scales."""
     assert input_ids.dim() == 2
     b, s0 = input_ids.shape
     cfg = model.config
@@ -281,17 +431,28 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     assert max_len <= cfg.max_position_embeddings, \
         (f"{max_len} tokens exceed max_position_embeddings="
          f"{cfg.max_position_embeddings}")
+    fp8 = _is_fp8(kv_dtype)
+    if kv_pool is not None:
+        if kv_dtype is not None and fp8 != kv_pool.fp8:
+            raise ValueError(
+                f"kv_dtype={kv_dtype!r} conflicts with kv_pool, which stores "
+                f"{'fp8' if kv_pool.fp8 else 'the model dtype'}")
+        fp8 = kv_pool.fp8
+    if kv_scales is not None and not fp8:
+        raise ValueError("kv_scales applies to an fp8 KV cache only")
     if page_size is not None or kv_pool is not None:
         pool = kv_pool
         if pool is None:
             pages = (max_len + page_size - 1) // page_size
             pool = PagedKVCache.for_model(model, b, b * pages, page_size,
-                                          max_len)
+                                          max_len, kv_dtype=kv_dtype)
         assert pool.b == b, \
             f"kv_pool serves {pool.b} sequences, the prompt has {b}"
         assert all(n == 0 for n in pool.owned[:b]), \
             "kv_pool sequences are still in use"
         pool.len = 0
+        if fp8:
+            _configure_scales(pool, kv_scales, kv_scale_headroom)
         try:
             return _generate_loop(model, input_ids, max_new_tokens,
                                   temperature, top_k, eos_token_id, pool)
@@ -301,9 +462,12 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     p = next(model.parameters())
     caches = [
         LayerKV(b, max_len, layer.self_attn.num_kv_heads,
-                layer.self_attn.head_dim, p.dtype, p.device)
+                layer.self_attn.head_dim, p.dtype, p.device,
+                kv_dtype=kv_dtype)
         for layer in model.layers
     ]
+    if fp8:
+        _configure_scales(caches, kv_scales, kv_scale_headroom)
     return _generate_loop(model, input_ids, max_new_tokens, temperature,
                           top_k, eos_token_id, caches)
 
@@ -365,10 +529,17 @@ class GraphDecoder:
     runs the paged decode op. The table and the lengths are device buffers
     read at replay, so a later ``decode`` may run with another page
     assignment (free and re-reserve in another order) without recapture.
+
+    With ``kv_dtype="fp8"`` the caches (contiguous or paged) hold e4m3 codes;
+    the captured step quantises its new rows with ``kv_cache_write_fp8`` and
+    the decode kernel reads the per-layer scale buffers at replay. Each
+    ``decode`` sets those buffers from its own prompt at prefill (or keeps
+    ``kv_scales``), so another prompt, with other scales, needs no recapture.
     """
 
     def __init__(self, model, b: int, max_len: int,
-                 page_size: Optional[int] = None):
+                 page_size: Optional[int] = None, kv_dtype=None,
+                 kv_scales=None, kv_scale_headroom: float = 2.0):
         p = next(model.parameters())
         assert p.is_cuda, "GraphDecoder requires a GPU model"
         self.model = model
@@ -379,18 +550,25 @@ class GraphDecoder:
         if page_size is None:
             self.caches = [
                 LayerKV(b, max_len, layer.self_attn.num_kv_heads, d, p.dtype,
-                        p.device)
+                        p.device, kv_dtype=kv_dtype)
                 for layer in model.layers
             ]
             self.k_lens = torch.zeros(b, dtype=torch.int32, device=dev)
         else:
             pages = (max_len + page_size - 1) // page_size
             self.paged = PagedKVCache.for_model(model, b, b * pages,
-                                                page_size, max_len)
+                                                page_size, max_len,
+                                                kv_dtype=kv_dtype)
             for i in range(b):
                 self.paged.reserve(i, max_len)
             self.caches = self.paged
             self.k_lens = self.paged.lens
+        self.fp8 = _is_fp8(kv_dtype)
+        if self.fp8:
+            _configure_scales(self.caches, kv_scales, kv_scale_headroom)
+        else:
+            assert kv_scales is None, \
+                "kv_scales applies to an fp8 KV cache only"
         self.ids = torch.zeros(b, 1, dtype=torch.long, device=dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=dev)
         self.graph = None
@@ -420,13 +598,16 @@ class GraphDecoder:
                 o = flash_attn_with_kvcache(
                     q, cache.k, cache.v, cache_seqlens=self.k_lens,
                     softmax_scale=attn.head_dim ** -0.5,
-                    block_table=self.paged.table)
+                    block_table=self.paged.table, **cache.scales())
             else:
-                cache.k.index_copy_(1, self.pos, k)
-                cache.v.index_copy_(1, self.pos, v)
+                if self.fp8:
+                    cache.write_at(k, v, self.pos)
+                else:
+                    cache.k.index_copy_(1, self.pos, k)
+                    cache.v.index_copy_(1, self.pos, v)
                 o = flash_attn_with_kvcache(
                     q, cache.k, cache.v, cache_seqlens=self.k_lens,
-                    softmax_scale=attn.head_dim ** -0.5)
+                    softmax_scale=attn.head_dim ** -0.5, **cache.scales())
             a = attn.o_proj(o.reshape(b, s, h * attn.head_dim))
             y2, resid2 = fused_add_rms_norm(
                 a, resid, layer.post_attention_layernorm.weight,

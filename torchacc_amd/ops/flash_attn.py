@@ -680,6 +680,73 @@ def _ref_decode(q, k_cache, v_cache, lens, softmax_scale, wl):
 _warned_decode = set()
 _NO_LENS = torch.empty(0)   # "no cache_seqlens" for ext.fa_decode
 
+# ---- fp8 KV cache: OCP e4m3fn codes with one fp32 scale per kv head --------
+FP8_DTYPE = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def _check_kv_scale(scale, cache, name):
+    assert isinstance(scale, torch.Tensor), \
+        f"fp8 KV caches need {name}: an fp32 tensor [hk]"
+    assert scale.dtype == torch.float32, \
+        f"{name} must be fp32, got {scale.dtype}"
+    assert scale.shape == (cache.shape[2],), \
+        f"{name} must be [hk] = [{cache.shape[2]}], got {tuple(scale.shape)}"
+    assert scale.device == cache.device, \
+        f"{name} must live on the device of the cache"
+
+
+def dequantize_kv_fp8(cache, scale, dtype=torch.float32):
+    """codes [.., .., hk, d] (float8_e4m3fn) * scale [hk] -> ``dtype``. The
+    product is formed in fp32 and rounded once."""
+    return (cache.float() * scale.view(1, 1, -1, 1)).to(dtype)
+
+
+def kv_cache_write_fp8(k, v, k_cache, v_cache, slots, k_scale, v_scale):
+    """Quantise new K / V rows into float8_e4m3fn caches, in place.
+
+    k, v [b, s, hk, d] (bf16/fp16 on the GPU; [hk, d] dense, d % 8 == 0);
+    k_cache, v_cache float8_e4m3fn [n0, n1, hk, d] with dense [hk, d] and
+    arbitrary strides for dims 0 and 1: a contiguous cache [b, cap, hk, d]
+    or a page pool [num_pages, page_size, hk, d]. ``slots`` (int32/int64
+    [b * s], same device) names the flat slot ``t -> [t // n1, t % n1]`` of
+    every token: ``PagedKVCache.slot_indices`` for a pool, ``batch * cap +
+    pos`` for a contiguous cache. k_scale, v_scale: fp32 [hk] on the device.
+
+    Every element becomes ``rne_e4m3(clamp(x * (1 / scale[head]), -448,
+    448))``: the clamp runs in fp32 before the conversion, so finite inputs
+    saturate and never turn into NaN. Slots outside [0, n0 * n1) are
+    skipped; duplicate slots are unspecified. One HIP launch for K and V
+    (csrc/kv_cache_write.hip), no host sync, no autograd."""
+    assert k.dim() == 4 and k.shape == v.shape and k.dtype == v.dtype
+    assert k_cache.dim() == 4 and k_cache.shape == v_cache.shape
+    assert k_cache.dtype == FP8_DTYPE and v_cache.dtype == FP8_DTYPE, \
+        "kv_cache_write_fp8 writes float8_e4m3fn caches"
+    assert k_cache.shape[2:] == k.shape[2:], \
+        "cache and new rows disagree on [hk, d]"
+    assert k.device == v.device == k_cache.device == v_cache.device
+    assert slots.dtype in (torch.int32, torch.int64), \
+        "slots must be int32 or int64"
+    assert slots.shape == (k.shape[0] * k.shape[1],) \
+        and slots.device == k.device, "slots must be [b * s] on k's device"
+    _check_kv_scale(k_scale, k_cache, "k_scale")
+    _check_kv_scale(v_scale, v_cache, "v_scale")
+    ext = dispatch(k)
+    if ext is not None:
+        ext.kv_cache_write_fp8(k, v, k_cache, v_cache, slots.contiguous(),
+                               k_scale, v_scale)
+        return
+    n0, n1 = k_cache.shape[:2]
+    t = slots.long()
+    ok = (t >= 0) & (t < n0 * n1)
+    t = t[ok]
+    for x, cache, scale in ((k, k_cache, k_scale), (v, v_cache, v_scale)):
+        y = x.float() * (1.0 / scale).view(1, 1, -1, 1)
+        codes = y.clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+        codes = codes.reshape(-1, *codes.shape[2:])[ok]
+        # no float8 index kernels on the CPU: store the bytes
+        cache.view(torch.uint8)[t // n1, t % n1] = codes.view(torch.uint8)
+
 
 def _decode_fallback_gpu(q, k_cache, v_cache, lens, softmax_scale, wl):
     """GPU inputs the decode kernel does not cover (fp32, head dims other
@@ -740,6 +807,10 @@ def _gather_pages(pool, block_table):
     n, ps, hk, d = pool.shape
     b, w = block_table.shape
     idx = block_table.reshape(-1).long().clamp(0, n - 1)
+    if pool.dtype == FP8_DTYPE:
+        # float8 has no index kernels on every backend: move the bytes
+        return (pool.view(torch.uint8).index_select(0, idx)
+                .view(b, w * ps, hk, d).view(FP8_DTYPE))
     return pool.index_select(0, idx).view(b, w * ps, hk, d)
 
 
@@ -788,9 +859,54 @@ def _decode_paged(q, k_pool, v_pool, lens, block_table, softmax_scale, wl,
                                 softmax_scale, wl)
 
 
+def _decode_fp8(q, k_cache, v_cache, lens, block_table, k_scale, v_scale,
+                softmax_scale, wl, num_splits):
+    """flash_attn_with_kvcache on float8_e4m3fn caches; returns (out, lse)."""
+    ext = dispatch(q)
+    if ext is None:
+        if block_table is not None:
+            assert lens is not None, \
+                "flash_attn_with_kvcache: block_table requires cache_seqlens"
+            k_cache = _gather_pages(k_cache, block_table)
+            v_cache = _gather_pages(v_cache, block_table)
+        return _ref_decode(q, dequantize_kv_fp8(k_cache, k_scale),
+                           dequantize_kv_fp8(v_cache, v_scale), lens,
+                           softmax_scale, wl)
+    kernel = (q.dtype in (torch.float16, torch.bfloat16)
+              and q.shape[-1] in (64, 128))
+    if block_table is None:
+        if kernel:
+            return ext.fa_decode_fp8(
+                q.contiguous(), k_cache, v_cache,
+                lens.contiguous() if lens is not None else _NO_LENS,
+                k_scale, v_scale, softmax_scale, wl, num_splits)
+        return _decode_fallback_gpu(
+            q, dequantize_kv_fp8(k_cache, k_scale, q.dtype),
+            dequantize_kv_fp8(v_cache, v_scale, q.dtype), lens,
+            softmax_scale, wl)
+    if kernel and _paged_kernel_page_size(k_cache.shape[1]):
+        assert lens is not None, \
+            "flash_attn_with_kvcache: block_table requires cache_seqlens"
+        assert block_table.dim() == 2 and block_table.shape[0] == q.shape[0]
+        assert block_table.dtype in (torch.int32, torch.int64), \
+            "block_table must be int32 or int64"
+        assert block_table.device == q.device, \
+            "block_table must live on the device of q"
+        return ext.fa_decode_paged_fp8(
+            q.contiguous(), k_cache, v_cache, lens.contiguous(),
+            block_table.to(torch.int32).contiguous(), k_scale, v_scale,
+            softmax_scale, wl, num_splits)
+    # not covered by the fp8 kernel: a copy of the pools in q's dtype takes
+    # the existing paths (and their once-per-combination warning)
+    return _decode_paged(q, dequantize_kv_fp8(k_cache, k_scale, q.dtype),
+                         dequantize_kv_fp8(v_cache, v_scale, q.dtype), lens,
+                         block_table, softmax_scale, wl, num_splits)
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
                             softmax_scale=None, window_size=(-1, -1),
-                            num_splits=0, return_lse=False, block_table=None):
+                            num_splits=0, return_lse=False, block_table=None,
+                            k_scale=None, v_scale=None):
     """Single-query (decode) attention over a KV cache, inference only.
 
     q [b, 1, hq, d]; k_cache / v_cache [b, cap, hk, d] with hk | hq, read in
@@ -826,12 +942,39 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
     bitwise the contiguous kernel's on the gathered cache at the same
     ``num_splits``; other page sizes (and the dtypes / head dims named
     above) gather the pages into a contiguous copy on the device first.
+
+    fp8 caches: k_cache / v_cache may be ``torch.float8_e4m3fn`` codes (as
+    ``kv_cache_write_fp8`` writes them), in either layout, while q stays
+    bf16/fp16. Then ``k_scale`` and ``v_scale`` (fp32 [hk], on the device,
+    read by the kernel) are required and
+
+        score = softmax_scale * k_scale[kh] * (q . K8)
+        out   = v_scale[kh] * sum_j p_j V8_j,  lse = logsumexp(score)
+
+    k_scale is folded into the q pre-scale and v_scale multiplies the
+    normalised row once, so the kernel differs from the 16-bit one by the
+    fp8 -> fp32 conversions only; paged fp8 is again bitwise contiguous fp8.
+    Inputs the kernel does not cover (fp32 q, other head dims, other page
+    sizes) dequantise the cache to a copy in q's dtype on the device and
+    take the paths above. Without scales and with caches of q's dtype
+    nothing changes.
     """
     assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
         "expected q [b, 1, hq, d] and caches [b, cap, hk, d]"
     assert q.shape[1] == 1, \
         f"flash_attn_with_kvcache takes one query per sequence, got {q.shape[1]}"
-    assert q.dtype == k_cache.dtype == v_cache.dtype
+    fp8 = k_cache.dtype == FP8_DTYPE or v_cache.dtype == FP8_DTYPE
+    if fp8:
+        assert k_cache.dtype == v_cache.dtype, \
+            "k_cache and v_cache must both be float8_e4m3fn"
+        assert k_scale is not None and v_scale is not None, \
+            "float8_e4m3fn caches need k_scale and v_scale (fp32 [hk])"
+        _check_kv_scale(k_scale, k_cache, "k_scale")
+        _check_kv_scale(v_scale, v_cache, "v_scale")
+    else:
+        assert k_scale is None and v_scale is None, \
+            "k_scale / v_scale apply to float8_e4m3fn caches only"
+        assert q.dtype == k_cache.dtype == v_cache.dtype
     assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
     assert q.device == k_cache.device == v_cache.device
     assert k_cache.shape == v_cache.shape
@@ -855,7 +998,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
     wl = int(window_size[0])
 
     ext = dispatch(q)
-    if block_table is not None:
+    if fp8:
+        out, lse = _decode_fp8(q, k_cache, v_cache, lens, block_table,
+                               k_scale, v_scale, softmax_scale, wl,
+                               num_splits)
+    elif block_table is not None:
         out, lse = _decode_paged(q, k_cache, v_cache, lens, block_table,
                                  softmax_scale, wl, num_splits)
     elif ext is None:
