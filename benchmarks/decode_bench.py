@@ -27,7 +27,17 @@ def main():
                    help="hipGraph-captured decode step (greedy)")
     p.add_argument("--kv-dtype", default=None, choices=["fp8"],
                    help="KV cache storage (default: the model dtype)")
+    p.add_argument("--page-size", type=int, default=None,
+                   help="paged KV cache with this page size (eager path)")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="run the prompt in pieces of at most this many "
+                        "tokens (eager path)")
     args = p.parse_args()
+    gen_kw = {"kv_dtype": args.kv_dtype}
+    if args.page_size is not None:
+        gen_kw["page_size"] = args.page_size
+    if args.prefill_chunk is not None:
+        gen_kw["prefill_chunk"] = args.prefill_chunk
 
     from torchacc_amd.models import (LlamaForCausalLM, llama_2_7b,
                                      llama_3_8b, llama_tiny)
@@ -56,13 +66,11 @@ def main():
         t0 = time.perf_counter()
         out = dec.decode(ids, args.new)
     else:
-        model.generate(ids, max_new_tokens=args.warmup,
-                       kv_dtype=args.kv_dtype)  # warm
+        model.generate(ids, max_new_tokens=args.warmup, **gen_kw)  # warm
         if on_gpu:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = model.generate(ids, max_new_tokens=args.new,
-                             kv_dtype=args.kv_dtype)
+        out = model.generate(ids, max_new_tokens=args.new, **gen_kw)
     if on_gpu:
         torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -76,6 +84,8 @@ def main():
         "dtype": "bf16" if on_gpu else "fp32",
         "graph": args.graph,
         "kv_dtype": args.kv_dtype or ("bf16" if on_gpu else "fp32"),
+        "page_size": args.page_size, "prefill_chunk": args.prefill_chunk,
+        "seconds": t1 - t0,
     }))
 
 

@@ -23,6 +23,7 @@ sources = [
         "flash_attn_bwd.hip",
         "flash_attn_varlen.hip",
         "flash_attn_decode.hip",
+        "flash_attn_kvcache_mq.hip",
         "kv_cache_write.hip",
         "flash_attn_extra_fwd.hip",
         "flash_attn_extra_bwd.hip",

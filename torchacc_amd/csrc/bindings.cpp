@@ -92,6 +92,27 @@ std::vector<torch::Tensor> fa_decode_paged_fp8(
     torch::Tensor k_lens, torch::Tensor block_table, torch::Tensor k_scale,
     torch::Tensor v_scale, double softmax_scale, long wl, long num_splits);
 
+// flash_attn_kvcache_mq.hip
+std::vector<torch::Tensor> fa_kvcache_mq(torch::Tensor q,
+                                         torch::Tensor k_cache,
+                                         torch::Tensor v_cache,
+                                         torch::Tensor k_lens,
+                                         torch::Tensor q_lens,
+                                         double softmax_scale, long wl);
+std::vector<torch::Tensor> fa_kvcache_mq_paged(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
+    double softmax_scale, long wl);
+std::vector<torch::Tensor> fa_kvcache_mq_fp8(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor k_scale,
+    torch::Tensor v_scale, double softmax_scale, long wl);
+std::vector<torch::Tensor> fa_kvcache_mq_paged_fp8(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
+    torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
+    long wl);
+
 // kv_cache_write.hip
 void kv_cache_write_fp8(torch::Tensor k, torch::Tensor v,
                         torch::Tensor k_cache, torch::Tensor v_cache,
@@ -128,6 +149,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_decode_paged", &fa_decode_paged);
   m.def("fa_decode_fp8", &fa_decode_fp8);
   m.def("fa_decode_paged_fp8", &fa_decode_paged_fp8);
+  m.def("fa_kvcache_mq", &fa_kvcache_mq);
+  m.def("fa_kvcache_mq_paged", &fa_kvcache_mq_paged);
+  m.def("fa_kvcache_mq_fp8", &fa_kvcache_mq_fp8);
+  m.def("fa_kvcache_mq_paged_fp8", &fa_kvcache_mq_paged_fp8);
   m.def("kv_cache_write_fp8", &kv_cache_write_fp8);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);
   m.def("lt_gemm", &lt_gemm, pybind11::arg("a"), pybind11::arg("b"),

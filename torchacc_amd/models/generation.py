@@ -18,10 +18,12 @@ the full-tile flash attention.
 With ``page_size`` the caches are a ``PagedKVCache``: fixed-size pages drawn
 from one pool per layer as a sequence grows and returned when it ends, named
 by one block table that all layers share. The decode kernel's paged variant
-differs from the contiguous one in its address computation only. Not
-covered: a continuous-batching scheduler, ragged prompts, prefix-cache
-management and a paged prefill kernel (prefill attends the prompt's own
-K/V and scatters them into the pages).
+differs from the contiguous one in its address computation only. A fresh
+prefill attends the prompt's own K/V and scatters them into the pages;
+several new tokens against a non-empty paged or fp8 cache (``prefill_chunk``)
+run ``flash_attn_chunk_with_kvcache``, which reads the cache in place. Not
+covered: a continuous-batching scheduler, ragged prompts and prefix-cache
+management.
 
 With ``kv_dtype="fp8"`` either cache stores OCP e4m3fn codes (one byte per
 element, half the pool and half the bytes a decode step reads) with one fp32
@@ -43,7 +45,8 @@ from typing import List, Optional
 
 import torch
 
-from ..ops.flash_attn import (FP8_DTYPE, FP8_MAX, dequantize_kv_fp8,
+from ..ops.flash_attn import (FP8_DTYPE, FP8_MAX,
+                              flash_attn_chunk_with_kvcache,
                               flash_attn_with_kvcache, flash_attn_xla,
                               kv_cache_write_fp8)
 from ..ops.rmsnorm import fused_add_rms_norm
@@ -315,14 +318,12 @@ def _attn_paged(q, k, v, cache: _PagedLayer, window):
     if pc.len == 0:
         # prefill: the prompt attends its own freshly computed K/V
         return flash_attn_xla(q, k, v, causal=True, window_size=window)
-    # several new tokens against a non-empty paged cache (generate never
-    # does this): there is no paged prefill kernel, so gather the live pages
-    # into a contiguous copy
-    kc, vc = pc.gather(cache.index, pc.len + s)
-    if cache.fp8:
-        kc = dequantize_kv_fp8(kc, cache.k_scale, q.dtype)
-        vc = dequantize_kv_fp8(vc, cache.v_scale, q.dtype)
-    return flash_attn_xla(q, kc, vc, causal=True, window_size=window)
+    # several new tokens against a non-empty paged cache (a later chunk of a
+    # chunked prefill): the pages are read in place through the block table;
+    # pc.lens already counts the new tokens
+    return flash_attn_chunk_with_kvcache(
+        q, cache.k, cache.v, pc.lens, window_size=(window[0], -1),
+        block_table=pc.table, **cache.scales())
 
 
 def _attn_with_cache(attn, x, cos, sin, cache, window=(-1, -1)):
@@ -344,12 +345,13 @@ def _attn_with_cache(attn, x, cos, sin, cache, window=(-1, -1)):
         # decode: the strided view is read in place, no copy
         o = flash_attn_with_kvcache(q, kc, vc, window_size=(window[0], -1),
                                     **cache.scales())
+    elif cache.fp8 and not fresh:
+        # several new tokens against a non-empty fp8 cache (a later chunk of
+        # a chunked prefill): the codes are read in place
+        lens = torch.full((b,), cache.len, dtype=torch.int32, device=q.device)
+        o = flash_attn_chunk_with_kvcache(
+            q, kc, vc, lens, window_size=(window[0], -1), **cache.scales())
     elif cache.fp8:
-        if not fresh:
-            # several new tokens against a non-empty fp8 cache (generate
-            # never does this): attend a dequantised copy
-            k = dequantize_kv_fp8(kc, cache.k_scale, q.dtype)
-            v = dequantize_kv_fp8(vc, cache.v_scale, q.dtype)
         # prefill: the prompt attends its own unquantised K/V
         o = flash_attn_xla(q, k, v, causal=True, window_size=window)
     else:
@@ -404,8 +406,18 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
              page_size: Optional[int] = None,
              kv_pool: Optional[PagedKVCache] = None,
              kv_dtype=None, kv_scales=None,
-             kv_scale_headroom: float = 2.0) -> torch.Tensor:
+             kv_scale_headroom: float = 2.0,
+             prefill_chunk: Optional[int] = None) -> torch.Tensor:
     """Greedy (temperature=0) or sampled decode; returns [b, s + new].
+
+    ``prefill_chunk`` runs the prompt in pieces of at most that many tokens
+    (chunked prefill): the first piece as an ordinary prefill, every later
+    one against the cache filled so far. Paged and fp8 caches read the cache
+    in place through ``flash_attn_chunk_with_kvcache``; the 16-bit contiguous
+    cache keeps its ``flash_attn_xla`` call on the cache view. With an fp8
+    cache and no ``kv_scales`` the calibration sees the FIRST piece only:
+    K / V of later pieces beyond 448 * scale saturate, as decoded tokens
+    already do. None (the default) prefills the prompt in one step.
 
     ``page_size`` selects the paged KV cache: pages are reserved on demand
     as the length grows and the decode steps read them through the block
@@ -431,6 +443,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     assert max_len <= cfg.max_position_embeddings, \
         (f"{max_len} tokens exceed max_position_embeddings="
          f"{cfg.max_position_embeddings}")
+    assert prefill_chunk is None or prefill_chunk >= 1, \
+        f"prefill_chunk must be None or >= 1, got {prefill_chunk}"
     fp8 = _is_fp8(kv_dtype)
     if kv_pool is not None:
         if kv_dtype is not None and fp8 != kv_pool.fp8:
@@ -455,7 +469,8 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
             _configure_scales(pool, kv_scales, kv_scale_headroom)
         try:
             return _generate_loop(model, input_ids, max_new_tokens,
-                                  temperature, top_k, eos_token_id, pool)
+                                  temperature, top_k, eos_token_id, pool,
+                                  prefill_chunk)
         finally:
             for i in range(b):
                 pool.free(i)
@@ -469,7 +484,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int = 32,
     if fp8:
         _configure_scales(caches, kv_scales, kv_scale_headroom)
     return _generate_loop(model, input_ids, max_new_tokens, temperature,
-                          top_k, eos_token_id, caches)
+                          top_k, eos_token_id, caches, prefill_chunk)
 
 
 def _step(model, ids, caches, pos: int) -> torch.Tensor:
@@ -480,11 +495,22 @@ def _step(model, ids, caches, pos: int) -> torch.Tensor:
     return _forward_step(model, ids, caches, pos)
 
 
+def _prefill(model, input_ids, caches, prefill_chunk) -> torch.Tensor:
+    """Run the prompt through the model, whole or in pieces of at most
+    ``prefill_chunk`` tokens; returns the last position's logits."""
+    if prefill_chunk is None:
+        return _step(model, input_ids, caches, 0)
+    for pos in range(0, input_ids.shape[1], prefill_chunk):
+        logits = _step(model, input_ids[:, pos:pos + prefill_chunk], caches,
+                       pos)
+    return logits
+
+
 def _generate_loop(model, input_ids, max_new_tokens, temperature, top_k,
-                   eos_token_id, caches) -> torch.Tensor:
+                   eos_token_id, caches, prefill_chunk=None) -> torch.Tensor:
     b = input_ids.shape[0]
     out = input_ids
-    logits = _step(model, input_ids, caches, 0)
+    logits = _prefill(model, input_ids, caches, prefill_chunk)
     finished = torch.zeros(b, dtype=torch.bool, device=input_ids.device)
     for i in range(max_new_tokens):
         if temperature > 0.0:

@@ -223,12 +223,13 @@ class LlamaForCausalLM(nn.Module):
                  temperature: float = 0.0, top_k: int = 0,
                  eos_token_id=None, page_size=None,
                  kv_pool=None, kv_dtype=None, kv_scales=None,
-                 kv_scale_headroom: float = 2.0) -> torch.Tensor:
+                 kv_scale_headroom: float = 2.0,
+                 prefill_chunk=None) -> torch.Tensor:
         """KV-cache autoregressive decode (models/generation.py)."""
         from .generation import generate as _gen
         return _gen(self, input_ids, max_new_tokens, temperature, top_k,
                     eos_token_id, page_size, kv_pool, kv_dtype, kv_scales,
-                    kv_scale_headroom)
+                    kv_scale_headroom, prefill_chunk)
 
     def forward(self, input_ids: torch.Tensor,
                 labels: Optional[torch.Tensor] = None,

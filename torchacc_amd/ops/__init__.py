@@ -1,5 +1,6 @@
 """Ops facade (reference torchacc/ops/__init__.py:1-6)."""
 from .flash_attn import (  # noqa: F401
+    flash_attn_chunk_with_kvcache,
     flash_attn_func, flash_attn_kvpacked_xla, flash_attn_qkvpacked_xla,
     flash_attn_varlen_func, flash_attn_varlen_position_ids_xla,
     flash_attn_varlen_qkvpacked_xla, flash_attn_varlen_xla,

@@ -1019,3 +1019,192 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
     if return_lse:
         return out, lse
     return out
+
+
+# ---------------------------------------------------------------------------
+# several queries per sequence against a KV cache (chunked prefill,
+# speculative verification, mixed prefill / decode batches)
+# ---------------------------------------------------------------------------
+
+def _ref_chunk(q, k_cache, v_cache, lens, q_lens, softmax_scale, wl):
+    """fp32 reference for flash_attn_chunk_with_kvcache on a contiguous cache
+    [b, cap, hk, d]. With L = lens[i] clamped to [0, cap] and n = q_lens[i]
+    clamped to [0, sq] (sq without q_lens), row j < n sits at p = L - n + j
+    and sees the keys [lo, p], lo = max(0, p - wl) (0 without a window); rows
+    with j >= n or p < 0 see nothing: zero output, lse = -inf. Slots no row
+    of their sequence sees are dropped with ``torch.where`` before any
+    arithmetic, so their contents (even NaN) cannot matter. Pure device
+    arithmetic, no host sync. Returns (out [b, sq, hq, d], lse [b, hq, sq])."""
+    b, sq, hq, d = q.shape
+    cap, hk = k_cache.shape[1], k_cache.shape[2]
+    rep = hq // hk
+    dev = q.device
+    L = lens.long().clamp(0, cap).view(b, 1, 1)
+    if q_lens is None:
+        n = torch.full((b, 1, 1), sq, dtype=torch.long, device=dev)
+    else:
+        n = q_lens.long().clamp(0, sq).view(b, 1, 1)
+    j = torch.arange(sq, device=dev).view(1, sq, 1)
+    ik = torch.arange(cap, device=dev).view(1, 1, cap)
+    p = L - n + j                                        # [b,sq,1]
+    lo = (p - wl).clamp(min=0) if wl >= 0 else torch.zeros_like(p)
+    vis = (j < n) & (p >= 0) & (ik >= lo) & (ik <= p) & (ik < L)  # [b,sq,cap]
+    keep = vis.any(dim=1).view(b, 1, cap, 1)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    kf = torch.where(keep, k_cache.float().permute(0, 2, 1, 3), zero)
+    vf = torch.where(keep, v_cache.float().permute(0, 2, 1, 3), zero)
+    # head = kh * rep + r -> rows (r, j) of kv head kh
+    qf = q.float().view(b, sq, hk, rep, d).permute(0, 2, 3, 1, 4)
+    qf = qf.reshape(b, hk, rep * sq, d)
+    scores = torch.matmul(qf, kf.transpose(-1, -2)) * softmax_scale
+    scores = scores.view(b, hk, rep, sq, cap)
+    scores = scores.masked_fill(~vis.view(b, 1, 1, sq, cap), float("-inf"))
+    lse = torch.logsumexp(scores, dim=-1, keepdim=True)  # -inf if none seen
+    pr = torch.where(torch.isfinite(lse), torch.exp(scores - lse), zero)
+    out = torch.matmul(pr.view(b, hk, rep * sq, cap), vf)
+    out = out.view(b, hk, rep, sq, d).permute(0, 3, 1, 2, 4)
+    return (out.reshape(b, sq, hq, d).to(q.dtype),
+            lse.reshape(b, hq, sq))
+
+
+_warned_chunk = set()
+
+
+def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
+                                  q_seqlens=None, softmax_scale=None,
+                                  window_size=(-1, -1), return_lse=False,
+                                  block_table=None, k_scale=None,
+                                  v_scale=None):
+    """Attention of several new tokens per sequence over a KV cache,
+    inference only: chunked prefill, a shared cached prefix, speculative
+    verification (k draft tokens against the cache), mixed prefill / decode
+    batches.
+
+    q [b, sq, hq, d], sq >= 1. The caches, ``block_table``, ``k_scale`` /
+    ``v_scale`` and their checks are those of ``flash_attn_with_kvcache``:
+    contiguous [b, cap, hk, d] read in place, or page pools [num_pages,
+    page_size, hk, d] with a block table; 16-bit or ``float8_e4m3fn`` codes
+    with one fp32 scale per kv head.
+
+    ``cache_seqlens`` (int32/int64 [b], required) counts the live keys of
+    every sequence INCLUDING its new tokens: the caller has already written
+    them, as with the decode op, whose query sits at len - 1. ``q_seqlens``
+    (int32/int64 [b], default: sq everywhere) says how many of the sq rows of
+    sequence i are real; they are its LAST tokens. With L = cache_seqlens[i]
+    clamped to [0, cap] and n = q_seqlens[i] clamped to [0, sq]:
+
+      - row j < n sits at position p = L - n + j and sees the keys [lo, p],
+        lo = max(0, p - window_size[0]) with a left window, else 0;
+      - a row with j >= n, or with p < 0 (L < n), is a zero row with
+        lse = -inf.
+
+    Slots no row sees never influence the result, whatever they hold; table
+    entries of logical pages at or past ceil(L / page_size) are never
+    dereferenced. Both length tensors are read on the device: no host sync,
+    and a captured graph follows new values.
+
+    bf16/fp16 q with d in {64, 128} on the GPU (and, paged, a page size that
+    is a power of two >= 16) runs the HIP kernel of
+    csrc/flash_attn_kvcache_mq.hip: the GQA group is packed into the MFMA row
+    dimension, so K and V are read once per kv head. It is deterministic,
+    and the paged result is bitwise the contiguous one on the gathered cache.
+    It does not split the keys: one short chunk against a very long context
+    at batch 1 uses few workgroups. Other GPU inputs (fp32 q, other head
+    dims, other page sizes) gather / dequantise a copy on the device and run
+    an fp32 composite there, still without a host sync. Returns out [b, sq,
+    hq, d], and lse [b, hq, sq] (fp32, natural log) with ``return_lse``."""
+    assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
+        "expected q [b, sq, hq, d] and caches [b, cap, hk, d]"
+    assert q.shape[1] >= 1, "q needs at least one row per sequence"
+    fp8 = k_cache.dtype == FP8_DTYPE or v_cache.dtype == FP8_DTYPE
+    if fp8:
+        assert k_cache.dtype == v_cache.dtype, \
+            "k_cache and v_cache must both be float8_e4m3fn"
+        assert k_scale is not None and v_scale is not None, \
+            "float8_e4m3fn caches need k_scale and v_scale (fp32 [hk])"
+        _check_kv_scale(k_scale, k_cache, "k_scale")
+        _check_kv_scale(v_scale, v_cache, "v_scale")
+    else:
+        assert k_scale is None and v_scale is None, \
+            "k_scale / v_scale apply to float8_e4m3fn caches only"
+        assert q.dtype == k_cache.dtype == v_cache.dtype
+    assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    assert q.device == k_cache.device == v_cache.device
+    assert k_cache.shape == v_cache.shape
+    assert block_table is not None or q.shape[0] == k_cache.shape[0]
+    assert q.shape[3] == k_cache.shape[3]
+    assert q.shape[2] % k_cache.shape[2] == 0, "GQA requires h_k | h_q"
+    if torch.is_grad_enabled() and any(
+            t.requires_grad for t in (q, k_cache, v_cache)):
+        raise RuntimeError(
+            "flash_attn_chunk_with_kvcache is inference only (no backward); "
+            "call it under torch.no_grad() or detach the inputs")
+    b = q.shape[0]
+    assert isinstance(cache_seqlens, torch.Tensor), \
+        "flash_attn_chunk_with_kvcache requires cache_seqlens"
+    lens, q_lens = cache_seqlens, q_seqlens
+    for name, t in (("cache_seqlens", lens), ("q_seqlens", q_lens)):
+        if t is None:
+            continue
+        assert t.dtype in (torch.int32, torch.int64), \
+            f"{name} must be int32 or int64"
+        assert t.shape == (b,) and t.device == q.device, \
+            f"{name} must be [b] on the device of q"
+    if lens.dtype != torch.int32:
+        lens = lens.to(torch.int32)         # device-side cast, no sync
+    if q_lens is not None and q_lens.dtype != torch.int32:
+        q_lens = q_lens.to(torch.int32)
+    if block_table is not None:
+        assert block_table.dim() == 2 and block_table.shape[0] == b, \
+            (f"block_table must be [batch, table_width], got "
+             f"{tuple(block_table.shape)} for batch {b}")
+        assert block_table.dtype in (torch.int32, torch.int64), \
+            "block_table must be int32 or int64"
+        assert block_table.device == q.device, \
+            "block_table must live on the device of q"
+        assert block_table.shape[1] >= 1 and k_cache.shape[0] >= 1
+        if block_table.dtype != torch.int32:
+            block_table = block_table.to(torch.int32)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    wl = int(window_size[0])
+
+    ext = dispatch(q)
+    kernel = (ext is not None
+              and q.dtype in (torch.float16, torch.bfloat16)
+              and q.shape[-1] in (64, 128)
+              and (block_table is None
+                   or _paged_kernel_page_size(k_cache.shape[1])))
+    if kernel:
+        ql = q_lens.contiguous() if q_lens is not None else _NO_LENS
+        args = [q.contiguous(), k_cache, v_cache, lens.contiguous(), ql]
+        if block_table is not None:
+            args.append(block_table.contiguous())
+        if fp8:
+            args += [k_scale, v_scale]
+        name = ("fa_kvcache_mq" + ("_paged" if block_table is not None else "")
+                + ("_fp8" if fp8 else ""))
+        out, lse = getattr(ext, name)(*args, softmax_scale, wl)
+    else:
+        if ext is not None:
+            key = (q.dtype, q.shape[-1],
+                   k_cache.shape[1] if block_table is not None else None, fp8)
+            if key not in _warned_chunk:
+                _warned_chunk.add(key)
+                from ..utils.logger import logger
+                logger.warning(
+                    "flash_attn_chunk_with_kvcache: dtype %s / head_dim %d / "
+                    "page_size %s / fp8 %s is not covered by the HIP kernel; "
+                    "running the fp32 composite on a copy of the cache on "
+                    "the device", *key)
+        if block_table is not None:
+            k_cache = _gather_pages(k_cache, block_table)
+            v_cache = _gather_pages(v_cache, block_table)
+        if fp8:
+            k_cache = dequantize_kv_fp8(k_cache, k_scale)
+            v_cache = dequantize_kv_fp8(v_cache, v_scale)
+        out, lse = _ref_chunk(q, k_cache, v_cache, lens, q_lens,
+                              softmax_scale, wl)
+    if return_lse:
+        return out, lse
+    return out
