@@ -66,48 +66,19 @@ std::vector<torch::Tensor> fa_varlen_backward(
     torch::Tensor out, torch::Tensor lse, torch::Tensor bounds,
     double softmax_scale, bool causal);
 
-// flash_attn_decode.hip
+// flash_attn_decode.hip; block_table / k_scale / v_scale: empty 1-d = absent
 std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
                                      torch::Tensor v_cache,
                                      torch::Tensor k_lens,
+                                     torch::Tensor block_table,
+                                     torch::Tensor k_scale,
+                                     torch::Tensor v_scale,
                                      double softmax_scale, long wl,
                                      long num_splits);
-std::vector<torch::Tensor> fa_decode_paged(torch::Tensor q,
-                                           torch::Tensor k_cache,
-                                           torch::Tensor v_cache,
-                                           torch::Tensor k_lens,
-                                           torch::Tensor block_table,
-                                           double softmax_scale, long wl,
-                                           long num_splits);
-std::vector<torch::Tensor> fa_decode_fp8(torch::Tensor q,
-                                         torch::Tensor k_cache,
-                                         torch::Tensor v_cache,
-                                         torch::Tensor k_lens,
-                                         torch::Tensor k_scale,
-                                         torch::Tensor v_scale,
-                                         double softmax_scale, long wl,
-                                         long num_splits);
-std::vector<torch::Tensor> fa_decode_paged_fp8(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor k_lens, torch::Tensor block_table, torch::Tensor k_scale,
-    torch::Tensor v_scale, double softmax_scale, long wl, long num_splits);
 
-// flash_attn_kvcache_mq.hip
-std::vector<torch::Tensor> fa_kvcache_mq(torch::Tensor q,
-                                         torch::Tensor k_cache,
-                                         torch::Tensor v_cache,
-                                         torch::Tensor k_lens,
-                                         torch::Tensor q_lens,
-                                         double softmax_scale, long wl);
-std::vector<torch::Tensor> fa_kvcache_mq_paged(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
-    double softmax_scale, long wl);
-std::vector<torch::Tensor> fa_kvcache_mq_fp8(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor k_scale,
-    torch::Tensor v_scale, double softmax_scale, long wl);
-std::vector<torch::Tensor> fa_kvcache_mq_paged_fp8(
+// flash_attn_kvcache_mq.hip; q_lens / block_table / k_scale / v_scale: empty
+// 1-d = absent
+std::vector<torch::Tensor> fa_kvcache_mq(
     torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
     torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
@@ -146,13 +117,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_varlen_forward", &fa_varlen_forward);
   m.def("fa_varlen_backward", &fa_varlen_backward);
   m.def("fa_decode", &fa_decode);
-  m.def("fa_decode_paged", &fa_decode_paged);
-  m.def("fa_decode_fp8", &fa_decode_fp8);
-  m.def("fa_decode_paged_fp8", &fa_decode_paged_fp8);
   m.def("fa_kvcache_mq", &fa_kvcache_mq);
-  m.def("fa_kvcache_mq_paged", &fa_kvcache_mq_paged);
-  m.def("fa_kvcache_mq_fp8", &fa_kvcache_mq_fp8);
-  m.def("fa_kvcache_mq_paged_fp8", &fa_kvcache_mq_paged_fp8);
   m.def("kv_cache_write_fp8", &kv_cache_write_fp8);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);
   m.def("lt_gemm", &lt_gemm, pybind11::arg("a"), pybind11::arg("b"),

@@ -44,19 +44,26 @@
 // entries of keys < end are read (never those of logical pages past the
 // live length), and each is clamped into [0, num_pages - 1] before use.
 //
-// fp8 variant (fa_decode_split_fp8_kernel): K and V hold OCP e4m3fn codes
-// (one byte per element) with one fp32 scale per kv head each; q, the output
-// and all arithmetic stay as they are. The lane mapping is unchanged: D/8
-// lanes per key, 8 elements per lane, so a lane's load is 8 bytes instead of 16 and
+// fp8 variant (FP8 = true): K and V hold OCP e4m3fn codes (one byte per
+// element) with one fp32 scale per kv head each; q, the output and all
+// arithmetic stay as they are. The lane mapping is unchanged: D/8 lanes per
+// key, 8 elements per lane, so a lane's load is 8 bytes instead of 16 and
 // slot, dofs, the tile loop, the split chunks and the merge order are those
 // of the 16-bit kernel. k_scale[kh] is folded into the q pre-scale and
 // v_scale[kh] multiplies the normalised row once in the epilogue, so the
 // inner loop gains only the fp8 -> fp32 conversions (v_cvt_pk_f32_fp8, two
 // elements each). Both scales are read from device memory by the kernel.
+//
+// There is one kernel, parameterised on how a lane holds its 8 cache elements
+// (DecCache). The scales travel in DecScales<FP8>, which is
+// empty without FP8, so the 16-bit instances keep the argument list they had
+// before the fp8 cache existed (register figures and the assembly
+// comparison: profiles/r10_kvcache_refactor.md).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
 #include "attn_common.h"
+#include "kvcache_common.h"
 
 namespace {
 
@@ -90,25 +97,59 @@ DEVINLINE float dec_group_sum(float v) {
   return v;
 }
 
+// How a lane holds the 8 cache elements it loads at once: 16-bit elements of
+// q's type (16 bytes), or e4m3 codes (8 bytes). Their conversion to fp32 is
+// written out under `if constexpr (FP8)` in the kernel, not as a member
+// here: routed through a helper, the 16-bit loops came out of the compiler
+// in another schedule and the paged 8-row instances ran 2-5 % slower
+// (profiles/r10_kvcache_refactor.md).
+template <bool FP8>
+struct DecCache {
+  using elem = short;
+  using vec8 = s16x8;
+  static DEVINLINE vec8 zero() { return s16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
+};
+
+template <>
+struct DecCache<true> {
+  using elem = unsigned char;
+  using vec8 = u32x2;
+  static DEVINLINE vec8 zero() { return u32x2{}; }
+};
+
+// fp32 [hk] each, read by the kernel. Empty for the 16-bit caches, whose
+// kernel then receives no scale pointers.
+template <bool FP8>
+struct DecScales {};
+
+template <>
+struct DecScales<true> {
+  const float* k;
+  const float* v;
+};
+
 // In HIP the second launch-bounds argument is the minimum number of waves
 // per execution unit (SIMD), not blocks per CU: 2 gives a 256-VGPR budget.
-template <int D, int R, bool FP16, bool PAGED>
+template <int D, int R, bool FP16, bool PAGED, bool FP8>
 __global__ __launch_bounds__(DEC_THREADS, 2)
-void fa_decode_split_kernel(const short* __restrict__ Q,
-                            const short* __restrict__ K,
-                            const short* __restrict__ V,
-                            const int* __restrict__ k_lens,
-                            short* __restrict__ O, float* __restrict__ LSE,
-                            float* __restrict__ o_part,
-                            float* __restrict__ lse_part, int cap, int hq,
-                            int hk, long k_sb, long k_ss, long v_sb,
-                            long v_ss, float scale_log2, int wl,
-                            int num_splits,
-                            // PAGED only: k_sb / v_sb are the page strides,
-                            // cap = table_width << page_shift
-                            const int* __restrict__ block_table,
-                            int page_shift, int num_pages) {
+void fa_decode_split_kernel(
+    const short* __restrict__ Q,
+    // FP8: K / V point at bytes and every cache stride counts bytes
+    const typename DecCache<FP8>::elem* __restrict__ K,
+    const typename DecCache<FP8>::elem* __restrict__ V,
+    const int* __restrict__ k_lens, short* __restrict__ O,
+    float* __restrict__ LSE, float* __restrict__ o_part,
+    float* __restrict__ lse_part, int cap, int hq, int hk, long k_sb,
+    long k_ss, long v_sb, long v_ss, float scale_log2, int wl,
+    int num_splits,
+    // PAGED only: k_sb / v_sb are the page strides, cap = table_width <<
+    // page_shift
+    const int* __restrict__ block_table, int page_shift, int num_pages,
+    DecScales<FP8> scales) {
   using ET = AttnElem<FP16>;
+  using KC = DecCache<FP8>;
+  using KE = typename KC::elem;
+  using KV8 = typename KC::vec8;
   constexpr int LPK = D / 8;          // lanes per key
   constexpr int KPW = 64 / LPK;       // keys per wave per load
   constexpr int S = 4 * KPW;          // key slots per workgroup
@@ -156,294 +197,9 @@ void fa_decode_split_kernel(const short* __restrict__ Q,
   }
 
   // ---- q rows, pre-scaled by softmax_scale * log2(e), fp32 ---------------
-  float q[R][8];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    s16x8 v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (r < nrows)
-      v = *reinterpret_cast<const s16x8*>(Q + (long)(b * hq + h0 + r) * D +
-                                          dofs);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[r][j] = ET::to_f32(v[j]) * scale_log2;
-  }
-
-  const short* kp = K + (PAGED ? 0L : (long)b * k_sb) + (long)kh * D + dofs;
-  const short* vp = V + (PAGED ? 0L : (long)b * v_sb) + (long)kh * D + dofs;
-
-  // PAGED: this sequence's table row, and the clamped physical pages of the
-  // U keys a lane owns in a tile. Entries are read for keys < end only, i.e.
-  // for logical pages < ceil(len / page_size): a lane whose key lies past
-  // the chunk reads the entry of key end - 1 instead (begin < end here), so
-  // the load needs no branch and the U loads of a tile issue back to back.
-  const int* bt = PAGED ? block_table + (long)b * (cap >> page_shift) : nullptr;
-  auto load_pages = [&](int key0, int* pg) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int key = min(key0 + u * S + slot, end - 1);
-      pg[u] = min(max(bt[key >> page_shift], 0), num_pages - 1);
-    }
-  };
-
-  // keys outside [begin, end) are not loaded: their registers are zero
-  auto load_tile = [&](const short* base, long sb, long ss, int key0,
-                       const int* pg, s16x8* reg) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int key = key0 + u * S + slot;
-      if constexpr (PAGED) {
-        const int in_page = key & ((1 << page_shift) - 1);
-        reg[u] = (key < end)
-                     ? *reinterpret_cast<const s16x8*>(
-                           base + (long)pg[u] * sb + (long)in_page * ss)
-                     : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      } else {
-        reg[u] = (key < end)
-                     ? *reinterpret_cast<const s16x8*>(base + (long)key * ss)
-                     : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    }
-  };
-
-  float m[R], l[R], acc[R][8];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    m[r] = -INFINITY;
-    l[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[r][j] = 0.f;
-  }
-
-  s16x8 kreg[U], vreg[U];
-  // pg: pages of the tile whose K/V are loaded next; pg_ahead: the tile
-  // after that, in flight while this tile computes (PAGED only)
-  int pg[U], pg_ahead[U];
-  if constexpr (PAGED) load_pages(begin, pg);
-  load_tile(kp, k_sb, k_ss, begin, pg, kreg);
-  load_tile(vp, v_sb, v_ss, begin, pg, vreg);
-  if constexpr (PAGED) load_pages(begin + DEC_TK, pg);
-
-  for (int kt = begin; kt < end; kt += DEC_TK) {
-    if constexpr (PAGED) load_pages(kt + 2 * DEC_TK, pg_ahead);
-    // ---- scores: s[r][u] = q[r] . K[key_u], log2 domain ------------------
-    float s[R][U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float kf[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) kf[j] = ET::to_f32(kreg[u][j]);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a = fmaf(q[r][j], kf[j], a);
-        s[r][u] = a;
-      }
-    }
-    // K registers are free: the next tile's K flies under softmax and PV
-    load_tile(kp, k_sb, k_ss, kt + DEC_TK, pg, kreg);
-
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const bool valid = (kt + u * S + slot) < end;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const float t = dec_group_sum<LPK>(s[r][u]);
-        s[r][u] = valid ? t : -INFINITY;
-      }
-    }
-
-    // ---- online softmax per key group ------------------------------------
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float mx = s[r][0];
-#pragma unroll
-      for (int u = 1; u < U; ++u) mx = fmaxf(mx, s[r][u]);
-      const float m_new = fmaxf(m[r], mx);
-      const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-      const float alpha = exp2f(m[r] - m_use);  // m = -inf -> 0
-      float ps = 0.f;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[r][u] = exp2f(s[r][u] - m_use);       // masked -> 0
-        ps += s[r][u];
-      }
-      l[r] = l[r] * alpha + ps;
-      m[r] = m_new;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[r][j] *= alpha;
-    }
-
-    // ---- acc[r] += p[r][u] * V[key_u] ------------------------------------
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float vf[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vf[j] = ET::to_f32(vreg[u][j]);
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          acc[r][j] = fmaf(s[r][u], vf[j], acc[r][j]);
-    }
-    load_tile(vp, v_sb, v_ss, kt + DEC_TK, pg, vreg);
-    if constexpr (PAGED) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) pg[u] = pg_ahead[u];
-    }
-  }
-
-  // ---- merge the key groups of a wave (fixed butterfly order) ------------
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    float mw = m[r];
-#pragma unroll
-    for (int off = LPK; off < 64; off <<= 1)
-      mw = fmaxf(mw, __shfl_xor(mw, off, 64));
-    const float m_use = (mw == -INFINITY) ? 0.f : mw;
-    const float sc = exp2f(m[r] - m_use);
-    float lr = l[r] * sc;
-#pragma unroll
-    for (int off = LPK; off < 64; off <<= 1) lr += __shfl_xor(lr, off, 64);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float a = acc[r][j] * sc;
-#pragma unroll
-      for (int off = LPK; off < 64; off <<= 1) a += __shfl_xor(a, off, 64);
-      acc[r][j] = a;
-    }
-    m[r] = mw;
-    l[r] = lr;
-  }
-  if (lane < LPK) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o_lds[wid][r][dofs + j] = acc[r][j];
-      if (lane == 0) {
-        m_lds[wid][r] = m[r];
-        l_lds[wid][r] = l[r];
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- merge the 4 waves, normalise, store -------------------------------
-  for (int e = tid; e < nrows * D; e += DEC_THREADS) {
-    const int r = e / D, d = e % D;
-    float mm = m_lds[0][r];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) mm = fmaxf(mm, m_lds[w][r]);
-    const float m_use = (mm == -INFINITY) ? 0.f : mm;
-    float lsum = 0.f, o = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float sc = exp2f(m_lds[w][r] - m_use);
-      lsum += l_lds[w][r] * sc;
-      o += o_lds[w][r][d] * sc;
-    }
-    const float on = (lsum > 0.f) ? o / lsum : 0.f;
-    const float lse = (lsum > 0.f) ? mm * LN2 + __logf(lsum) : -INFINITY;
-    const long row = b * hq + h0 + r;
-    if (num_splits == 1) {
-      O[row * D + d] = ET::from_f32(on);
-      if (d == 0) LSE[row] = lse;
-    } else {
-      o_part[(row * num_splits + split) * D + d] = on;
-      if (d == 0) lse_part[row * num_splits + split] = lse;
-    }
-  }
-}
-
-// 8 e4m3 codes of one lane as fp32
-DEVINLINE void dec_cvt8_fp8(const u32x2& r, float* f) {
-#pragma unroll
-  for (int w = 0; w < 2; ++w) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[w], false);
-    const f32x2 b = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[w], true);
-    f[4 * w + 0] = a[0];
-    f[4 * w + 1] = a[1];
-    f[4 * w + 2] = b[0];
-    f[4 * w + 3] = b[1];
-  }
-}
-
-// fa_decode_split_kernel for float8_e4m3fn caches (see the header comment).
-// A sibling, not a flag: the 16-bit kernel above stays as it was compiled,
-// with its register figures. Everything not marked "fp8:" is that kernel's
-// text; K / V point at bytes and every cache stride counts bytes.
-template <int D, int R, bool FP16, bool PAGED>
-__global__ __launch_bounds__(DEC_THREADS, 2)
-void fa_decode_split_fp8_kernel(const short* __restrict__ Q,
-                                const unsigned char* __restrict__ K,
-                                const unsigned char* __restrict__ V,
-                                const int* __restrict__ k_lens,
-                                short* __restrict__ O,
-                                float* __restrict__ LSE,
-                                float* __restrict__ o_part,
-                                float* __restrict__ lse_part, int cap, int hq,
-                                int hk, long k_sb, long k_ss, long v_sb,
-                                long v_ss, float scale_log2, int wl,
-                                int num_splits,
-                                // PAGED only: k_sb / v_sb are the page
-                                // strides, cap = table_width << page_shift
-                                const int* __restrict__ block_table,
-                                int page_shift, int num_pages,
-                                // fp8: fp32 [hk] each
-                                const float* __restrict__ k_scale,
-                                const float* __restrict__ v_scale) {
-  using ET = AttnElem<FP16>;
-  // fp8: cache element and the 8 elements a lane loads at once (8 bytes)
-  using KE = unsigned char;
-  using KV8 = u32x2;
-  constexpr int LPK = D / 8;          // lanes per key
-  constexpr int KPW = 64 / LPK;       // keys per wave per load
-  constexpr int S = 4 * KPW;          // key slots per workgroup
-  constexpr int DEC_TK = dec_tile_keys(D, R);
-  constexpr int U = DEC_TK / S;       // keys per lane per tile
-  constexpr float LN2 = 0.6931471805599453f;
-
-  __shared__ float o_lds[4][R][D];
-  __shared__ float m_lds[4][R];
-  __shared__ float l_lds[4][R];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int slot = wid * KPW + lane / LPK;
-  const int dofs = (lane % LPK) * 8;
-
-  const int split = blockIdx.x;
-  const int rep = hq / hk;
-  const int ngroups = (rep + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
-  const int kh = blockIdx.y / ngroups;
-  const int g = blockIdx.y % ngroups;
-  const int b = blockIdx.z;
-  const int h0 = kh * rep + g * DEC_MAX_ROWS;          // first q head
-  const int nrows = min(R, rep - g * DEC_MAX_ROWS);    // real q rows
-
-  // ---- this split's key chunk, from the device-side length --------------
-  int klen = cap;
-  if (k_lens != nullptr) klen = min(max(k_lens[b], 0), cap);
-  const int lo = (wl >= 0) ? max(0, klen - 1 - wl) : 0;
-  const int tiles = (klen - lo + DEC_TK - 1) / DEC_TK;
-  const int tps = (tiles + num_splits - 1) / num_splits;  // tiles per split
-  const int begin = lo + split * tps * DEC_TK;
-  const int end = min(klen, begin + tps * DEC_TK);
-
-  if (begin >= end) {  // empty split (uniform over the workgroup)
-    if (num_splits == 1) {
-      for (int e = tid; e < nrows * D; e += DEC_THREADS)
-        O[(long)(b * hq + h0) * D + e] = 0;
-      if (tid < nrows) LSE[b * hq + h0 + tid] = -INFINITY;
-    } else if (tid < nrows) {
-      lse_part[(long)(b * hq + h0 + tid) * num_splits + split] = -INFINITY;
-    }
-    return;
-  }
-
-  // ---- q rows, pre-scaled by softmax_scale * log2(e), fp32 ---------------
-  // fp8: times k_scale[kh], so the scores are those of the scaled keys
-  const float q_scale = scale_log2 * k_scale[kh];
+  // FP8: times k_scale[kh], so the scores are those of the scaled keys
+  float q_scale = scale_log2;
+  if constexpr (FP8) q_scale = scale_log2 * scales.k[kh];
   float q[R][8];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -483,11 +239,11 @@ void fa_decode_split_fp8_kernel(const short* __restrict__ Q,
         reg[u] = (key < end)
                      ? *reinterpret_cast<const KV8*>(
                            base + (long)pg[u] * sb + (long)in_page * ss)
-                     : KV8{};
+                     : KC::zero();
       } else {
         reg[u] = (key < end)
                      ? *reinterpret_cast<const KV8*>(base + (long)key * ss)
-                     : KV8{};
+                     : KC::zero();
       }
     }
   };
@@ -517,7 +273,12 @@ void fa_decode_split_fp8_kernel(const short* __restrict__ Q,
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float kf[8];
-      dec_cvt8_fp8(kreg[u], kf);
+      if constexpr (FP8) {
+        kvc_cvt8_fp8(kreg[u], kf);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) kf[j] = ET::to_f32(kreg[u][j]);
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         float a = 0.f;
@@ -564,7 +325,12 @@ void fa_decode_split_fp8_kernel(const short* __restrict__ Q,
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float vf[8];
-      dec_cvt8_fp8(vreg[u], vf);
+      if constexpr (FP8) {
+        kvc_cvt8_fp8(vreg[u], vf);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vf[j] = ET::to_f32(vreg[u][j]);
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -614,7 +380,8 @@ void fa_decode_split_fp8_kernel(const short* __restrict__ Q,
   __syncthreads();
 
   // ---- merge the 4 waves, normalise, store -------------------------------
-  const float o_scale = v_scale[kh];   // fp8: once per normalised row
+  float o_scale = 1.f;   // FP8: v_scale[kh], once per normalised row
+  if constexpr (FP8) o_scale = scales.v[kh];
   for (int e = tid; e < nrows * D; e += DEC_THREADS) {
     const int r = e / D, d = e % D;
     float mm = m_lds[0][r];
@@ -628,7 +395,8 @@ void fa_decode_split_fp8_kernel(const short* __restrict__ Q,
       lsum += l_lds[w][r] * sc;
       o += o_lds[w][r][d] * sc;
     }
-    const float on = ((lsum > 0.f) ? o / lsum : 0.f) * o_scale;
+    float on = (lsum > 0.f) ? o / lsum : 0.f;
+    if constexpr (FP8) on *= o_scale;
     const float lse = (lsum > 0.f) ? mm * LN2 + __logf(lsum) : -INFINITY;
     const long row = b * hq + h0 + r;
     if (num_splits == 1) {
@@ -685,42 +453,28 @@ int choose_num_splits(int b, int hk_groups, int cap, int num_cus) {
   return (int)std::max<long>(s, 1);
 }
 
-// Contiguous: k / v are [b, cap, hk, d] and bt is null. Paged: k / v are
-// pools [num_pages, page_size, hk, d], bt is the [b, cap >> page_shift]
-// table; the strides handed to the kernel are then the page and slot strides.
+// Contiguous: k / v are [b, cap, hk, d]. Paged: k / v are pools [num_pages,
+// page_size, hk, d] and the strides handed to the kernel are the page and
+// slot strides.
 template <int D, int R, bool FP16, bool PAGED, bool FP8>
 void launch_decode(const torch::Tensor& q, const torch::Tensor& k,
                    const torch::Tensor& v, const int* klp, torch::Tensor& o,
                    torch::Tensor& lse, float* o_part, float* lse_part,
                    float scale_log2, int wl, int num_splits, int groups,
-                   hipStream_t stream, int cap, const int* bt,
-                   int page_shift, const float* k_scale,
-                   const float* v_scale) {
+                   hipStream_t stream, const KvcGeometry& geo,
+                   DecScales<FP8> scales) {
+  using KE = typename DecCache<FP8>::elem;
   const int b = q.size(0), hq = q.size(2);
   const int hk = k.size(2);
-  const int num_pages = PAGED ? (int)k.size(0) : 0;
   dim3 grid(num_splits, hk * groups, b);
-  if constexpr (FP8) {
-    using byte = unsigned char;
-    hipLaunchKernelGGL((fa_decode_split_fp8_kernel<D, R, FP16, PAGED>), grid,
-                       dim3(DEC_THREADS), 0, stream,
-                       (const short*)q.data_ptr(), (const byte*)k.data_ptr(),
-                       (const byte*)v.data_ptr(), klp, (short*)o.data_ptr(),
-                       lse.data_ptr<float>(), o_part, lse_part, cap, hq, hk,
-                       (long)k.stride(0), (long)k.stride(1),
-                       (long)v.stride(0), (long)v.stride(1), scale_log2, wl,
-                       num_splits, bt, page_shift, num_pages, k_scale,
-                       v_scale);
-  } else {
-    hipLaunchKernelGGL((fa_decode_split_kernel<D, R, FP16, PAGED>), grid,
-                       dim3(DEC_THREADS), 0, stream,
-                       (const short*)q.data_ptr(), (const short*)k.data_ptr(),
-                       (const short*)v.data_ptr(), klp, (short*)o.data_ptr(),
-                       lse.data_ptr<float>(), o_part, lse_part, cap, hq, hk,
-                       (long)k.stride(0), (long)k.stride(1),
-                       (long)v.stride(0), (long)v.stride(1), scale_log2, wl,
-                       num_splits, bt, page_shift, num_pages);
-  }
+  hipLaunchKernelGGL((fa_decode_split_kernel<D, R, FP16, PAGED, FP8>), grid,
+                     dim3(DEC_THREADS), 0, stream, (const short*)q.data_ptr(),
+                     (const KE*)k.data_ptr(), (const KE*)v.data_ptr(), klp,
+                     (short*)o.data_ptr(), lse.data_ptr<float>(), o_part,
+                     lse_part, (int)geo.cap, hq, hk, (long)k.stride(0),
+                     (long)k.stride(1), (long)v.stride(0), (long)v.stride(1),
+                     scale_log2, wl, num_splits, geo.table, geo.page_shift,
+                     geo.num_pages, scales);
   if (num_splits > 1) {
     hipLaunchKernelGGL((fa_decode_combine_kernel<D, FP16>), dim3(b * hq),
                        dim3(D), 0, stream, o_part, lse_part,
@@ -729,75 +483,46 @@ void launch_decode(const torch::Tensor& q, const torch::Tensor& k,
   }
 }
 
-void check_cache(const torch::Tensor& c, const torch::Tensor& q,
-                 const char* name, bool fp8 = false) {
-  TORCH_CHECK(c.is_cuda() && c.dim() == 4, "fa_decode: ", name,
-              " must be a 4-d GPU tensor");
-  TORCH_CHECK(c.stride(3) == 1 && c.stride(2) == c.size(3),
-              "fa_decode: ", name, " needs dense [heads][head_dim]");
-  if (fp8) {
-    TORCH_CHECK(c.scalar_type() == torch::kFloat8_e4m3fn, "fa_decode_fp8: ",
-                name, " must be float8_e4m3fn");
-    // 8-byte loads of one-byte elements: strides are bytes here
-    TORCH_CHECK(c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 == 0,
-                "fa_decode_fp8: ", name, " rows must be 8-byte aligned");
-    return;
-  }
-  TORCH_CHECK(c.scalar_type() == q.scalar_type(), "fa_decode: ", name,
-              " must be a 4-d GPU tensor of q's dtype");
-  // 16-byte loads
-  TORCH_CHECK(c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0,
-              "fa_decode: ", name, " rows must be 16-byte aligned");
-}
+constexpr const char* DEC_OP = "fa_decode";
 
-// fp8 caches: one fp32 scale per kv head, read by the kernel
-const float* check_scale(const torch::Tensor& s, const torch::Tensor& cache,
-                         const char* name) {
-  TORCH_CHECK(s.is_cuda() && s.scalar_type() == torch::kFloat32 &&
-                  s.dim() == 1 && s.size(0) == cache.size(2) &&
-                  s.is_contiguous() && s.device() == cache.device(),
-              "fa_decode_fp8: ", name, " must be a GPU fp32 [hk]");
-  return s.data_ptr<float>();
-}
-
-void check_q(const torch::Tensor& q) {
+// All checks, the split choice, the workspace and the launches. hk =
+// k_cache.size(2) in both layouts.
+template <bool PAGED, bool FP8>
+std::vector<torch::Tensor> run_decode(const torch::Tensor& q,
+                                      const torch::Tensor& k_cache,
+                                      const torch::Tensor& v_cache,
+                                      const torch::Tensor& k_lens,
+                                      const torch::Tensor& block_table,
+                                      const torch::Tensor& k_scale,
+                                      const torch::Tensor& v_scale,
+                                      double softmax_scale, long wl,
+                                      long num_splits) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.is_contiguous() &&
                   q.size(1) == 1,
               "fa_decode: q must be a contiguous GPU [b, 1, hq, d]");
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 ||
                   q.scalar_type() == torch::kHalf,
               "fa_decode: bf16/fp16 only");
-}
+  kvc_check_cache(DEC_OP, k_cache, q, "k_cache", FP8);
+  kvc_check_cache(DEC_OP, v_cache, q, "v_cache", FP8);
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
+              "fa_decode: k_cache and v_cache shapes differ");
+  const KvcGeometry geo = kvc_check_geometry(DEC_OP, q, k_cache, block_table);
+  // without a table, absent lengths mean "every sequence is cap long"
+  const int* klp = nullptr;
+  if (PAGED || kvc_present(k_lens))
+    klp = kvc_check_lens(DEC_OP, k_lens, q, "k_lens");
+  DecScales<FP8> scales;
+  if constexpr (FP8) {
+    scales.k = kvc_check_scale(DEC_OP, k_scale, k_cache, "k_scale");
+    scales.v = kvc_check_scale(DEC_OP, v_scale, v_cache, "v_scale");
+  }
 
-const int* check_lens(const torch::Tensor& k_lens, long b) {
-  TORCH_CHECK(k_lens.is_cuda() && k_lens.scalar_type() == torch::kInt32 &&
-                  k_lens.dim() == 1 && k_lens.size(0) == b &&
-                  k_lens.is_contiguous(),
-              "fa_decode: k_lens must be a GPU int32 [b]");
-  return k_lens.data_ptr<int>();
-}
-
-// Shared tail of fa_decode / fa_decode_paged: shape checks that hold for
-// both layouts, split choice, workspace, launches. `cap` is the contiguous
-// capacity or table_width * page_size; hk = k.size(2) in both layouts.
-template <bool PAGED, bool FP8>
-std::vector<torch::Tensor> run_decode(const torch::Tensor& q,
-                                      const torch::Tensor& k_cache,
-                                      const torch::Tensor& v_cache,
-                                      const int* klp, long cap,
-                                      const int* bt, int page_shift,
-                                      double softmax_scale, long wl,
-                                      long num_splits,
-                                      const float* k_scale = nullptr,
-                                      const float* v_scale = nullptr) {
   const long b = q.size(0), hq = q.size(2), D = q.size(3);
   const long hk = k_cache.size(2);
   TORCH_CHECK(D == 64 || D == 128, "fa_decode: head_dim must be 64 or 128");
-  TORCH_CHECK(k_cache.size(3) == D);
   TORCH_CHECK(hk > 0 && hq % hk == 0, "fa_decode: needs h_k | h_q");
-  TORCH_CHECK(b >= 1 && b <= 65535 && cap >= 1 && cap <= (1L << 30));
+  TORCH_CHECK(b >= 1 && b <= 65535);
   TORCH_CHECK(num_splits >= 0 && num_splits <= 65535,
               "fa_decode: num_splits must be in [0, 65535]");
   wl = std::min<long>(wl, 1L << 30);  // anything larger is "no window"
@@ -808,7 +533,7 @@ std::vector<torch::Tensor> run_decode(const torch::Tensor& q,
   int ns = (int)num_splits;
   if (ns == 0)
     ns = choose_num_splits(
-        (int)b, (int)hk * groups, (int)cap,
+        (int)b, (int)hk * groups, (int)geo.cap,
         at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
 
   auto o = torch::empty_like(q);
@@ -828,8 +553,7 @@ std::vector<torch::Tensor> run_decode(const torch::Tensor& q,
   FP16_SWITCH(q.scalar_type() == torch::kHalf,                               \
               launch_decode<DD, RR, kFP16, PAGED, FP8>(                      \
                   q, k_cache, v_cache, klp, o, lse, opp, lpp, scale_log2,    \
-                  (int)wl, ns, groups, stream, (int)cap, bt, page_shift,     \
-                  k_scale, v_scale))
+                  (int)wl, ns, groups, stream, geo, scales))
 #define DEC_ROWS(DD)                                                         \
   do {                                                                       \
     if (rep == 1) DEC_LAUNCH(DD, 1);                                         \
@@ -844,114 +568,28 @@ std::vector<torch::Tensor> run_decode(const torch::Tensor& q,
   return {o, lse};
 }
 
-// Contiguous layout; k_scale / v_scale are null for the 16-bit caches.
-template <bool FP8>
-std::vector<torch::Tensor> decode_contiguous(
-    const torch::Tensor& q, const torch::Tensor& k_cache,
-    const torch::Tensor& v_cache, const torch::Tensor& k_lens,
-    double softmax_scale, long wl, long num_splits, const float* k_scale,
-    const float* v_scale) {
-  check_q(q);
-  check_cache(k_cache, q, "k_cache", FP8);
-  check_cache(v_cache, q, "v_cache", FP8);
-  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
-              "fa_decode: k_cache and v_cache shapes differ");
-  TORCH_CHECK(k_cache.size(0) == q.size(0));
-  const int* klp = nullptr;
-  if (k_lens.numel() > 0) klp = check_lens(k_lens, q.size(0));
-  return run_decode<false, FP8>(q, k_cache, v_cache, klp, k_cache.size(1),
-                                nullptr, 0, softmax_scale, wl, num_splits,
-                                k_scale, v_scale);
-}
-
-// Paged layout: k_cache / v_cache are page pools [num_pages, page_size, hk,
-// d], block_table is int32 [b, table_width]. Shape-only checks, no host
-// sync: the table's contents are never read on the host (the kernel clamps
-// every entry it dereferences into the pool).
-template <bool FP8>
-std::vector<torch::Tensor> decode_paged(
-    const torch::Tensor& q, const torch::Tensor& k_cache,
-    const torch::Tensor& v_cache, const torch::Tensor& k_lens,
-    const torch::Tensor& block_table, double softmax_scale, long wl,
-    long num_splits, const float* k_scale, const float* v_scale) {
-  check_q(q);
-  check_cache(k_cache, q, "k_cache", FP8);
-  check_cache(v_cache, q, "v_cache", FP8);
-  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
-              "fa_decode_paged: k_cache and v_cache shapes differ");
-  const long b = q.size(0);
-  const long num_pages = k_cache.size(0), ps = k_cache.size(1);
-  TORCH_CHECK(num_pages >= 1 && num_pages <= (1L << 30),
-              "fa_decode_paged: the pool needs 1..2^30 pages");
-  TORCH_CHECK(ps >= 16 && (ps & (ps - 1)) == 0,
-              "fa_decode_paged: page_size must be a power of two >= 16, got ",
-              ps);
-  TORCH_CHECK(block_table.is_cuda() &&
-                  block_table.scalar_type() == torch::kInt32 &&
-                  block_table.dim() == 2 && block_table.size(0) == b &&
-                  block_table.is_contiguous(),
-              "fa_decode_paged: block_table must be a contiguous GPU int32 "
-              "[b, table_width]");
-  const long tw = block_table.size(1);
-  TORCH_CHECK(tw >= 1 && tw * ps <= (1L << 30),
-              "fa_decode_paged: table_width * page_size must be in "
-              "[1, 2^30]");
-  const int* klp = check_lens(k_lens, b);
-  int shift = 0;
-  while ((1L << shift) < ps) ++shift;
-  return run_decode<true, FP8>(q, k_cache, v_cache, klp, tw * ps,
-                               block_table.data_ptr<int>(), shift,
-                               softmax_scale, wl, num_splits, k_scale,
-                               v_scale);
-}
-
 }  // namespace
 
+// block_table, k_scale and v_scale are optional: an undefined or empty 1-d
+// tensor means absent (so does k_lens, without a table). With a table the
+// caches are
+// page pools. With scales (fp32 [hk] on the device, both or neither) they
+// hold float8_e4m3fn codes: score = softmax_scale * k_scale[kh] * (q . K8),
+// out = v_scale[kh] * sum p V8.
 std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
                                      torch::Tensor v_cache,
                                      torch::Tensor k_lens,
+                                     torch::Tensor block_table,
+                                     torch::Tensor k_scale,
+                                     torch::Tensor v_scale,
                                      double softmax_scale, long wl,
                                      long num_splits) {
-  return decode_contiguous<false>(q, k_cache, v_cache, k_lens, softmax_scale,
-                                  wl, num_splits, nullptr, nullptr);
+  const bool fp8 = kvc_present(k_scale);
+  TORCH_CHECK(fp8 == kvc_present(v_scale),
+              "fa_decode: k_scale and v_scale come together");
+  auto run = kvc_present(block_table)
+                 ? (fp8 ? run_decode<true, true> : run_decode<true, false>)
+                 : (fp8 ? run_decode<false, true> : run_decode<false, false>);
+  return run(q, k_cache, v_cache, k_lens, block_table, k_scale, v_scale,
+             softmax_scale, wl, num_splits);
 }
-
-std::vector<torch::Tensor> fa_decode_paged(torch::Tensor q,
-                                           torch::Tensor k_cache,
-                                           torch::Tensor v_cache,
-                                           torch::Tensor k_lens,
-                                           torch::Tensor block_table,
-                                           double softmax_scale, long wl,
-                                           long num_splits) {
-  return decode_paged<false>(q, k_cache, v_cache, k_lens, block_table,
-                             softmax_scale, wl, num_splits, nullptr, nullptr);
-}
-
-// float8_e4m3fn caches with per-kv-head fp32 scales [hk] on the device:
-// score = softmax_scale * k_scale[kh] * (q . K8), out = v_scale[kh] * sum p V8.
-std::vector<torch::Tensor> fa_decode_fp8(torch::Tensor q,
-                                         torch::Tensor k_cache,
-                                         torch::Tensor v_cache,
-                                         torch::Tensor k_lens,
-                                         torch::Tensor k_scale,
-                                         torch::Tensor v_scale,
-                                         double softmax_scale, long wl,
-                                         long num_splits) {
-  TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4);
-  const float* ks = check_scale(k_scale, k_cache, "k_scale");
-  const float* vs = check_scale(v_scale, v_cache, "v_scale");
-  return decode_contiguous<true>(q, k_cache, v_cache, k_lens, softmax_scale,
-                                 wl, num_splits, ks, vs);
-}
-
-std::vector<torch::Tensor> fa_decode_paged_fp8(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor k_lens, torch::Tensor block_table, torch::Tensor k_scale,
-    torch::Tensor v_scale, double softmax_scale, long wl, long num_splits) {
-  TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4);
-  const float* ks = check_scale(k_scale, k_cache, "k_scale");
-  const float* vs = check_scale(v_scale, v_cache, "v_scale");
-  return decode_paged<true>(q, k_cache, v_cache, k_lens, block_table,
-                            softmax_scale, wl, num_splits, ks, vs);
-}
-

@@ -53,6 +53,7 @@
 #include <type_traits>
 #include "common.h"
 #include "attn_common.h"
+#include "kvcache_common.h"
 
 namespace {
 
@@ -78,19 +79,14 @@ DEVINLINE unsigned mq_pack_exact(float lo, float hi) {
 // 8 e4m3 codes -> 8 16-bit elements (exact)
 template <bool FP16>
 DEVINLINE s16x8 mq_cvt8_fp8(const u32x2& r) {
-  unsigned w[4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[i], false);
-    const f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[i], true);
-    w[2 * i + 0] = mq_pack_exact<FP16>(a[0], a[1]);
-    w[2 * i + 1] = mq_pack_exact<FP16>(c[0], c[1]);
-  }
+  float f[8];
+  kvc_cvt8_fp8(r, f);
   s16x8 out;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    out[2 * i + 0] = (short)(w[i] & 0xffffu);
-    out[2 * i + 1] = (short)(w[i] >> 16);
+    const unsigned w = mq_pack_exact<FP16>(f[2 * i], f[2 * i + 1]);
+    out[2 * i + 0] = (short)(w & 0xffffu);
+    out[2 * i + 1] = (short)(w >> 16);
   }
   return out;
 }
@@ -435,49 +431,6 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
 // host side
 // ---------------------------------------------------------------------------
 
-void mq_check_cache(const torch::Tensor& c, const torch::Tensor& q,
-                    const char* name, bool fp8) {
-  TORCH_CHECK(c.is_cuda() && c.dim() == 4 && c.device() == q.device(),
-              "fa_kvcache_mq: ", name, " must be a 4-d tensor on q's GPU");
-  TORCH_CHECK(c.stride(3) == 1 && c.stride(2) == c.size(3),
-              "fa_kvcache_mq: ", name, " needs dense [heads][head_dim]");
-  TORCH_CHECK(c.size(3) == q.size(3), "fa_kvcache_mq: ", name,
-              " and q disagree on head_dim");
-  if (fp8) {
-    TORCH_CHECK(c.scalar_type() == torch::kFloat8_e4m3fn,
-                "fa_kvcache_mq_fp8: ", name, " must be float8_e4m3fn");
-    // 8-byte loads of one-byte elements: strides are bytes here
-    TORCH_CHECK(c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
-                    reinterpret_cast<uintptr_t>(c.data_ptr()) % 8 == 0,
-                "fa_kvcache_mq_fp8: ", name, " rows must be 8-byte aligned");
-    return;
-  }
-  TORCH_CHECK(c.scalar_type() == q.scalar_type(), "fa_kvcache_mq: ", name,
-              " must have q's dtype");
-  // 16-byte loads
-  TORCH_CHECK(c.stride(0) % 8 == 0 && c.stride(1) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0,
-              "fa_kvcache_mq: ", name, " rows must be 16-byte aligned");
-}
-
-const int* mq_check_lens(const torch::Tensor& lens, const torch::Tensor& q,
-                         const char* name) {
-  TORCH_CHECK(lens.is_cuda() && lens.device() == q.device() &&
-                  lens.scalar_type() == torch::kInt32 && lens.dim() == 1 &&
-                  lens.size(0) == q.size(0) && lens.is_contiguous(),
-              "fa_kvcache_mq: ", name, " must be an int32 [b] on q's GPU");
-  return lens.data_ptr<int>();
-}
-
-const float* mq_check_scale(const torch::Tensor& s,
-                            const torch::Tensor& cache, const char* name) {
-  TORCH_CHECK(s.is_cuda() && s.scalar_type() == torch::kFloat32 &&
-                  s.dim() == 1 && s.size(0) == cache.size(2) &&
-                  s.is_contiguous() && s.device() == cache.device(),
-              "fa_kvcache_mq_fp8: ", name, " must be a GPU fp32 [hk]");
-  return s.data_ptr<float>();
-}
-
 template <int D, bool FP16, bool PAGED, bool FP8>
 void mq_launch(const torch::Tensor& q, const torch::Tensor& k,
                const torch::Tensor& v, const int* klp, const int* qlp,
@@ -500,9 +453,9 @@ void mq_launch(const torch::Tensor& q, const torch::Tensor& k,
                      v_scale);
 }
 
-// block_table undefined (numel 0, dim != 2) -> contiguous [b, cap, hk, d];
-// otherwise pools [num_pages, page_size, hk, d] and an int32 [b, width]
-// table. Shape-only checks, no host sync.
+constexpr const char* MQ_OP = "fa_kvcache_mq";
+
+// Shape-only checks, no host sync.
 template <bool PAGED, bool FP8>
 std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
                                   const torch::Tensor& k_cache,
@@ -510,7 +463,8 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
                                   const torch::Tensor& k_lens,
                                   const torch::Tensor& q_lens,
                                   const torch::Tensor& block_table,
-                                  const float* k_scale, const float* v_scale,
+                                  const torch::Tensor& k_scale,
+                                  const torch::Tensor& v_scale,
                                   double softmax_scale, long wl) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.is_contiguous(),
               "fa_kvcache_mq: q must be a contiguous GPU [b, sq, hq, d]");
@@ -518,8 +472,8 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
                   q.scalar_type() == torch::kHalf,
               "fa_kvcache_mq: bf16/fp16 only");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0);
-  mq_check_cache(k_cache, q, "k_cache", FP8);
-  mq_check_cache(v_cache, q, "v_cache", FP8);
+  kvc_check_cache(MQ_OP, k_cache, q, "k_cache", FP8);
+  kvc_check_cache(MQ_OP, v_cache, q, "v_cache", FP8);
   TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
               "fa_kvcache_mq: k_cache and v_cache shapes differ");
   const long b = q.size(0), sq = q.size(1), hq = q.size(2), D = q.size(3);
@@ -530,39 +484,14 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
   TORCH_CHECK(b >= 1 && b <= 65535 && hk <= 65535 && sq >= 1 &&
                   sq * (hq / hk) <= (1L << 30),
               "fa_kvcache_mq: batch / heads / rows out of range");
-  const int* klp = mq_check_lens(k_lens, q, "k_lens");
+  const int* klp = kvc_check_lens(MQ_OP, k_lens, q, "k_lens");
   const int* qlp = nullptr;
-  if (q_lens.numel() > 0) qlp = mq_check_lens(q_lens, q, "q_lens");
-
-  long cap;
-  const int* bt = nullptr;
-  int page_shift = 0;
-  if constexpr (PAGED) {
-    const long num_pages = k_cache.size(0), ps = k_cache.size(1);
-    TORCH_CHECK(num_pages >= 1 && num_pages <= (1L << 30),
-                "fa_kvcache_mq_paged: the pool needs 1..2^30 pages");
-    TORCH_CHECK(ps >= 16 && (ps & (ps - 1)) == 0,
-                "fa_kvcache_mq_paged: page_size must be a power of two "
-                ">= 16, got ", ps);
-    TORCH_CHECK(block_table.is_cuda() &&
-                    block_table.device() == q.device() &&
-                    block_table.scalar_type() == torch::kInt32 &&
-                    block_table.dim() == 2 && block_table.size(0) == b &&
-                    block_table.is_contiguous(),
-                "fa_kvcache_mq_paged: block_table must be a contiguous GPU "
-                "int32 [b, table_width]");
-    const long tw = block_table.size(1);
-    TORCH_CHECK(tw >= 1 && tw * ps <= (1L << 30),
-                "fa_kvcache_mq_paged: table_width * page_size must be in "
-                "[1, 2^30]");
-    cap = tw * ps;
-    bt = block_table.data_ptr<int>();
-    while ((1L << page_shift) < ps) ++page_shift;
-  } else {
-    TORCH_CHECK(k_cache.size(0) == b,
-                "fa_kvcache_mq: cache and q disagree on the batch");
-    cap = k_cache.size(1);
-    TORCH_CHECK(cap >= 1 && cap <= (1L << 30));
+  if (kvc_present(q_lens)) qlp = kvc_check_lens(MQ_OP, q_lens, q, "q_lens");
+  const KvcGeometry geo = kvc_check_geometry(MQ_OP, q, k_cache, block_table);
+  const float *ks = nullptr, *vs = nullptr;
+  if constexpr (FP8) {
+    ks = kvc_check_scale(MQ_OP, k_scale, k_cache, "k_scale");
+    vs = kvc_check_scale(MQ_OP, v_scale, v_cache, "v_scale");
   }
   wl = std::min<long>(wl, 1L << 30);  // anything larger is "no window"
 
@@ -572,9 +501,9 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
 #define MQ_LAUNCH(DD)                                                        \
   FP16_SWITCH(q.scalar_type() == torch::kHalf,                               \
               mq_launch<DD, kFP16, PAGED, FP8>(                              \
-                  q, k_cache, v_cache, klp, qlp, o, lse, (int)cap,           \
-                  (float)softmax_scale, (int)wl, bt, page_shift, k_scale,    \
-                  v_scale, stream))
+                  q, k_cache, v_cache, klp, qlp, o, lse, (int)geo.cap,       \
+                  (float)softmax_scale, (int)wl, geo.table, geo.page_shift,  \
+                  ks, vs, stream))
   if (D == 128) MQ_LAUNCH(128); else MQ_LAUNCH(64);
 #undef MQ_LAUNCH
   HIP_CHECK_LAST();
@@ -583,47 +512,22 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
 
 }  // namespace
 
-std::vector<torch::Tensor> fa_kvcache_mq(torch::Tensor q,
-                                         torch::Tensor k_cache,
-                                         torch::Tensor v_cache,
-                                         torch::Tensor k_lens,
-                                         torch::Tensor q_lens,
-                                         double softmax_scale, long wl) {
-  return mq_run<false, false>(q, k_cache, v_cache, k_lens, q_lens,
-                              torch::Tensor(), nullptr, nullptr,
-                              softmax_scale, wl);
-}
-
-std::vector<torch::Tensor> fa_kvcache_mq_paged(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
-    double softmax_scale, long wl) {
-  return mq_run<true, false>(q, k_cache, v_cache, k_lens, q_lens,
-                             block_table, nullptr, nullptr, softmax_scale,
-                             wl);
-}
-
-// float8_e4m3fn caches with per-kv-head fp32 scales [hk] on the device:
-// score = softmax_scale * k_scale[kh] * (q . K8), out = v_scale[kh] * sum p V8.
-std::vector<torch::Tensor> fa_kvcache_mq_fp8(
-    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
-    torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor k_scale,
-    torch::Tensor v_scale, double softmax_scale, long wl) {
-  TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4);
-  const float* ks = mq_check_scale(k_scale, k_cache, "k_scale");
-  const float* vs = mq_check_scale(v_scale, v_cache, "v_scale");
-  return mq_run<false, true>(q, k_cache, v_cache, k_lens, q_lens,
-                             torch::Tensor(), ks, vs, softmax_scale, wl);
-}
-
-std::vector<torch::Tensor> fa_kvcache_mq_paged_fp8(
+// q_lens, block_table, k_scale and v_scale are optional: an undefined or
+// empty 1-d tensor means absent. With a table the caches are page pools
+// [num_pages, page_size, hk, d]. With scales (fp32 [hk] on the device, both
+// or neither) they hold float8_e4m3fn codes: score = softmax_scale *
+// k_scale[kh] * (q . K8), out = v_scale[kh] * sum p V8.
+std::vector<torch::Tensor> fa_kvcache_mq(
     torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
     torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
     long wl) {
-  TORCH_CHECK(k_cache.dim() == 4 && v_cache.dim() == 4);
-  const float* ks = mq_check_scale(k_scale, k_cache, "k_scale");
-  const float* vs = mq_check_scale(v_scale, v_cache, "v_scale");
-  return mq_run<true, true>(q, k_cache, v_cache, k_lens, q_lens, block_table,
-                            ks, vs, softmax_scale, wl);
+  const bool fp8 = kvc_present(k_scale);
+  TORCH_CHECK(fp8 == kvc_present(v_scale),
+              "fa_kvcache_mq: k_scale and v_scale come together");
+  auto run = kvc_present(block_table)
+                 ? (fp8 ? mq_run<true, true> : mq_run<true, false>)
+                 : (fp8 ? mq_run<false, true> : mq_run<false, false>);
+  return run(q, k_cache, v_cache, k_lens, q_lens, block_table, k_scale,
+             v_scale, softmax_scale, wl);
 }

@@ -678,7 +678,7 @@ def _ref_decode(q, k_cache, v_cache, lens, softmax_scale, wl):
 
 
 _warned_decode = set()
-_NO_LENS = torch.empty(0)   # "no cache_seqlens" for ext.fa_decode
+_ABSENT = torch.empty(0)    # an absent optional tensor, for the extension
 
 # ---- fp8 KV cache: OCP e4m3fn codes with one fp32 scale per kv head --------
 FP8_DTYPE = torch.float8_e4m3fn
@@ -818,89 +818,76 @@ def _paged_kernel_page_size(ps: int) -> bool:
     return ps >= 16 and (ps & (ps - 1)) == 0
 
 
-def _decode_paged(q, k_pool, v_pool, lens, block_table, softmax_scale, wl,
-                  num_splits):
-    """flash_attn_with_kvcache with a block table; returns (out, lse)."""
-    assert lens is not None, \
-        "flash_attn_with_kvcache: block_table requires cache_seqlens"
-    assert block_table.dim() == 2 and block_table.shape[0] == q.shape[0], \
-        (f"block_table must be [batch, table_width], got "
-         f"{tuple(block_table.shape)} for batch {q.shape[0]}")
-    assert block_table.dtype in (torch.int32, torch.int64), \
-        "block_table must be int32 or int64"
-    assert block_table.device == q.device, \
-        "block_table must live on the device of q"
-    assert block_table.shape[1] >= 1 and k_pool.shape[0] >= 1
-    assert q.shape[3] == k_pool.shape[3]
-    if block_table.dtype != torch.int32:
-        block_table = block_table.to(torch.int32)   # device-side, no sync
-    ps = k_pool.shape[1]
-
-    ext = dispatch(q)
-    if ext is None:
-        return _ref_decode(q, _gather_pages(k_pool, block_table),
-                           _gather_pages(v_pool, block_table), lens,
-                           softmax_scale, wl)
-    if (q.dtype in (torch.float16, torch.bfloat16)
-            and q.shape[-1] in (64, 128) and _paged_kernel_page_size(ps)):
-        return ext.fa_decode_paged(
-            q.contiguous(), k_pool, v_pool, lens.contiguous(),
-            block_table.contiguous(), softmax_scale, wl, num_splits)
-    key = ("paged", q.dtype, q.shape[-1], ps)
-    if key not in _warned_decode:
-        _warned_decode.add(key)
-        from ..utils.logger import logger
-        logger.warning(
-            "flash_attn_with_kvcache: dtype %s / head_dim %d / page_size %d "
-            "is not covered by the paged decode kernel; gathering the pages "
-            "into a contiguous copy on the device", *key[1:])
-    return _decode_fallback_gpu(q, _gather_pages(k_pool, block_table),
-                                _gather_pages(v_pool, block_table), lens,
-                                softmax_scale, wl)
-
-
-def _decode_fp8(q, k_cache, v_cache, lens, block_table, k_scale, v_scale,
-                softmax_scale, wl, num_splits):
-    """flash_attn_with_kvcache on float8_e4m3fn caches; returns (out, lse)."""
-    ext = dispatch(q)
-    if ext is None:
-        if block_table is not None:
-            assert lens is not None, \
-                "flash_attn_with_kvcache: block_table requires cache_seqlens"
-            k_cache = _gather_pages(k_cache, block_table)
-            v_cache = _gather_pages(v_cache, block_table)
-        return _ref_decode(q, dequantize_kv_fp8(k_cache, k_scale),
-                           dequantize_kv_fp8(v_cache, v_scale), lens,
-                           softmax_scale, wl)
-    kernel = (q.dtype in (torch.float16, torch.bfloat16)
-              and q.shape[-1] in (64, 128))
-    if block_table is None:
-        if kernel:
-            return ext.fa_decode_fp8(
-                q.contiguous(), k_cache, v_cache,
-                lens.contiguous() if lens is not None else _NO_LENS,
-                k_scale, v_scale, softmax_scale, wl, num_splits)
-        return _decode_fallback_gpu(
-            q, dequantize_kv_fp8(k_cache, k_scale, q.dtype),
-            dequantize_kv_fp8(v_cache, v_scale, q.dtype), lens,
-            softmax_scale, wl)
-    if kernel and _paged_kernel_page_size(k_cache.shape[1]):
-        assert lens is not None, \
-            "flash_attn_with_kvcache: block_table requires cache_seqlens"
-        assert block_table.dim() == 2 and block_table.shape[0] == q.shape[0]
+def _kvcache_args(op, q, k_cache, v_cache, cache_seqlens, q_seqlens,
+                  softmax_scale, window_size, block_table, k_scale, v_scale):
+    """What flash_attn_with_kvcache and flash_attn_chunk_with_kvcache share:
+    the argument checks, the lengths and the block table as int32 (device-side
+    casts, no sync), the default softmax scale, the left window and whether
+    the HIP kernels cover the combination. Straight-line code: the decode op
+    is launch-bound at short contexts. Returns (fp8, covered, lens, q_lens,
+    block_table, softmax_scale, wl). The caller has checked that q and the
+    caches are 4-d."""
+    fp8 =k_cache.dtype == FP8_DTYPE or v_cache.dtype == FP8_DTYPE
+    if fp8:
+        assert k_cache.dtype == v_cache.dtype, \
+            "k_cache and v_cache must both be float8_e4m3fn"
+        assert k_scale is not None and v_scale is not None, \
+            "float8_e4m3fn caches need k_scale and v_scale (fp32 [hk])"
+        _check_kv_scale(k_scale, k_cache, "k_scale")
+        _check_kv_scale(v_scale, v_cache, "v_scale")
+    else:
+        assert k_scale is None and v_scale is None, \
+            "k_scale / v_scale apply to float8_e4m3fn caches only"
+        assert q.dtype == k_cache.dtype == v_cache.dtype
+    assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
+    assert q.device == k_cache.device == v_cache.device
+    assert k_cache.shape == v_cache.shape
+    assert block_table is not None or q.shape[0] == k_cache.shape[0]
+    assert q.shape[3] == k_cache.shape[3]
+    assert q.shape[2] % k_cache.shape[2] == 0, "GQA requires h_k | h_q"
+    if torch.is_grad_enabled() and any(
+            t.requires_grad for t in (q, k_cache, v_cache)):
+        raise RuntimeError(
+            f"{op} is inference only (no backward); call it under "
+            "torch.no_grad() or detach the inputs")
+    b = q.shape[0]
+    lens, q_lens = cache_seqlens, q_seqlens
+    if lens is not None:
+        assert lens.dtype in (torch.int32, torch.int64), \
+            "cache_seqlens must be int32 or int64"
+        assert lens.shape == (b,) and lens.device == q.device, \
+            "cache_seqlens must be [b] on the device of q"
+        if lens.dtype != torch.int32:
+            lens = lens.to(torch.int32)
+    if q_lens is not None:
+        assert q_lens.dtype in (torch.int32, torch.int64), \
+            "q_seqlens must be int32 or int64"
+        assert q_lens.shape == (b,) and q_lens.device == q.device, \
+            "q_seqlens must be [b] on the device of q"
+        if q_lens.dtype != torch.int32:
+            q_lens = q_lens.to(torch.int32)
+    if block_table is not None:
+        assert cache_seqlens is not None, \
+            f"{op}: block_table requires cache_seqlens"
+        assert block_table.dim() == 2 and block_table.shape[0] == b, \
+            (f"block_table must be [batch, table_width], got "
+             f"{tuple(block_table.shape)} for batch {b}")
         assert block_table.dtype in (torch.int32, torch.int64), \
             "block_table must be int32 or int64"
         assert block_table.device == q.device, \
             "block_table must live on the device of q"
-        return ext.fa_decode_paged_fp8(
-            q.contiguous(), k_cache, v_cache, lens.contiguous(),
-            block_table.to(torch.int32).contiguous(), k_scale, v_scale,
-            softmax_scale, wl, num_splits)
-    # not covered by the fp8 kernel: a copy of the pools in q's dtype takes
-    # the existing paths (and their once-per-combination warning)
-    return _decode_paged(q, dequantize_kv_fp8(k_cache, k_scale, q.dtype),
-                         dequantize_kv_fp8(v_cache, v_scale, q.dtype), lens,
-                         block_table, softmax_scale, wl, num_splits)
+        assert block_table.shape[1] >= 1 and k_cache.shape[0] >= 1
+        if block_table.dtype != torch.int32:
+            block_table = block_table.to(torch.int32)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    # what the HIP kernels cover, given a GPU
+    covered = (q.dtype in (torch.float16, torch.bfloat16)
+               and q.shape[-1] in (64, 128)
+               and (block_table is None
+                    or _paged_kernel_page_size(k_cache.shape[1])))
+    return (fp8, covered, lens, q_lens, block_table, softmax_scale,
+            int(window_size[0]))
 
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
@@ -963,57 +950,46 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens=None,
         "expected q [b, 1, hq, d] and caches [b, cap, hk, d]"
     assert q.shape[1] == 1, \
         f"flash_attn_with_kvcache takes one query per sequence, got {q.shape[1]}"
-    fp8 = k_cache.dtype == FP8_DTYPE or v_cache.dtype == FP8_DTYPE
-    if fp8:
-        assert k_cache.dtype == v_cache.dtype, \
-            "k_cache and v_cache must both be float8_e4m3fn"
-        assert k_scale is not None and v_scale is not None, \
-            "float8_e4m3fn caches need k_scale and v_scale (fp32 [hk])"
-        _check_kv_scale(k_scale, k_cache, "k_scale")
-        _check_kv_scale(v_scale, v_cache, "v_scale")
-    else:
-        assert k_scale is None and v_scale is None, \
-            "k_scale / v_scale apply to float8_e4m3fn caches only"
-        assert q.dtype == k_cache.dtype == v_cache.dtype
-    assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
-    assert q.device == k_cache.device == v_cache.device
-    assert k_cache.shape == v_cache.shape
-    assert block_table is not None or q.shape[0] == k_cache.shape[0]
-    assert q.shape[3] == k_cache.shape[3]
-    assert q.shape[2] % k_cache.shape[2] == 0, "GQA requires h_k | h_q"
-    if torch.is_grad_enabled() and any(
-            t.requires_grad for t in (q, k_cache, v_cache)):
-        raise RuntimeError(
-            "flash_attn_with_kvcache is inference only (no backward); call "
-            "it under torch.no_grad() or detach the inputs")
-    lens = cache_seqlens
-    if lens is not None:
-        assert lens.dtype in (torch.int32, torch.int64), \
-            "cache_seqlens must be int32 or int64"
-        assert lens.shape == (q.shape[0],) and lens.device == q.device
-        if lens.dtype != torch.int32:
-            lens = lens.to(torch.int32)     # device-side cast, no sync
-    if softmax_scale is None:
-        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
-    wl = int(window_size[0])
+    fp8, covered, lens, _, block_table, softmax_scale, wl = _kvcache_args(
+        "flash_attn_with_kvcache", q, k_cache, v_cache, cache_seqlens, None,
+        softmax_scale, window_size, block_table, k_scale, v_scale)
+    paged = block_table is not None
 
     ext = dispatch(q)
-    if fp8:
-        out, lse = _decode_fp8(q, k_cache, v_cache, lens, block_table,
-                               k_scale, v_scale, softmax_scale, wl,
-                               num_splits)
-    elif block_table is not None:
-        out, lse = _decode_paged(q, k_cache, v_cache, lens, block_table,
-                                 softmax_scale, wl, num_splits)
-    elif ext is None:
+    if ext is None:
+        if paged:
+            k_cache = _gather_pages(k_cache, block_table)
+            v_cache = _gather_pages(v_cache, block_table)
+        if fp8:
+            k_cache = dequantize_kv_fp8(k_cache, k_scale)
+            v_cache = dequantize_kv_fp8(v_cache, v_scale)
         out, lse = _ref_decode(q, k_cache, v_cache, lens, softmax_scale, wl)
-    elif (q.dtype in (torch.float16, torch.bfloat16)
-          and q.shape[-1] in (64, 128)):
+    elif covered:
         out, lse = ext.fa_decode(
             q.contiguous(), k_cache, v_cache,
-            lens.contiguous() if lens is not None else _NO_LENS,
+            lens.contiguous() if lens is not None else _ABSENT,
+            block_table.contiguous() if paged else _ABSENT,
+            k_scale if fp8 else _ABSENT, v_scale if fp8 else _ABSENT,
             softmax_scale, wl, num_splits)
     else:
+        # not covered by the kernel: a copy of the cache in q's dtype,
+        # gathered if it is paged, takes the fixed-length path (each step
+        # warns once per combination)
+        if fp8:
+            k_cache = dequantize_kv_fp8(k_cache, k_scale, q.dtype)
+            v_cache = dequantize_kv_fp8(v_cache, v_scale, q.dtype)
+        if paged:
+            key = ("paged", q.dtype, q.shape[-1], k_cache.shape[1])
+            if key not in _warned_decode:
+                _warned_decode.add(key)
+                from ..utils.logger import logger
+                logger.warning(
+                    "flash_attn_with_kvcache: dtype %s / head_dim %d / "
+                    "page_size %d is not covered by the paged decode kernel; "
+                    "gathering the pages into a contiguous copy on the "
+                    "device", *key[1:])
+            k_cache = _gather_pages(k_cache, block_table)
+            v_cache = _gather_pages(v_cache, block_table)
         out, lse = _decode_fallback_gpu(q, k_cache, v_cache, lens,
                                         softmax_scale, wl)
     if return_lse:
@@ -1116,79 +1092,25 @@ def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
     assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
         "expected q [b, sq, hq, d] and caches [b, cap, hk, d]"
     assert q.shape[1] >= 1, "q needs at least one row per sequence"
-    fp8 = k_cache.dtype == FP8_DTYPE or v_cache.dtype == FP8_DTYPE
-    if fp8:
-        assert k_cache.dtype == v_cache.dtype, \
-            "k_cache and v_cache must both be float8_e4m3fn"
-        assert k_scale is not None and v_scale is not None, \
-            "float8_e4m3fn caches need k_scale and v_scale (fp32 [hk])"
-        _check_kv_scale(k_scale, k_cache, "k_scale")
-        _check_kv_scale(v_scale, v_cache, "v_scale")
-    else:
-        assert k_scale is None and v_scale is None, \
-            "k_scale / v_scale apply to float8_e4m3fn caches only"
-        assert q.dtype == k_cache.dtype == v_cache.dtype
-    assert q.dtype in (torch.float16, torch.bfloat16, torch.float32)
-    assert q.device == k_cache.device == v_cache.device
-    assert k_cache.shape == v_cache.shape
-    assert block_table is not None or q.shape[0] == k_cache.shape[0]
-    assert q.shape[3] == k_cache.shape[3]
-    assert q.shape[2] % k_cache.shape[2] == 0, "GQA requires h_k | h_q"
-    if torch.is_grad_enabled() and any(
-            t.requires_grad for t in (q, k_cache, v_cache)):
-        raise RuntimeError(
-            "flash_attn_chunk_with_kvcache is inference only (no backward); "
-            "call it under torch.no_grad() or detach the inputs")
-    b = q.shape[0]
     assert isinstance(cache_seqlens, torch.Tensor), \
         "flash_attn_chunk_with_kvcache requires cache_seqlens"
-    lens, q_lens = cache_seqlens, q_seqlens
-    for name, t in (("cache_seqlens", lens), ("q_seqlens", q_lens)):
-        if t is None:
-            continue
-        assert t.dtype in (torch.int32, torch.int64), \
-            f"{name} must be int32 or int64"
-        assert t.shape == (b,) and t.device == q.device, \
-            f"{name} must be [b] on the device of q"
-    if lens.dtype != torch.int32:
-        lens = lens.to(torch.int32)         # device-side cast, no sync
-    if q_lens is not None and q_lens.dtype != torch.int32:
-        q_lens = q_lens.to(torch.int32)
-    if block_table is not None:
-        assert block_table.dim() == 2 and block_table.shape[0] == b, \
-            (f"block_table must be [batch, table_width], got "
-             f"{tuple(block_table.shape)} for batch {b}")
-        assert block_table.dtype in (torch.int32, torch.int64), \
-            "block_table must be int32 or int64"
-        assert block_table.device == q.device, \
-            "block_table must live on the device of q"
-        assert block_table.shape[1] >= 1 and k_cache.shape[0] >= 1
-        if block_table.dtype != torch.int32:
-            block_table = block_table.to(torch.int32)
-    if softmax_scale is None:
-        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
-    wl = int(window_size[0])
+    fp8, covered, lens, q_lens, block_table, softmax_scale, wl = _kvcache_args(
+        "flash_attn_chunk_with_kvcache", q, k_cache, v_cache, cache_seqlens,
+        q_seqlens, softmax_scale, window_size, block_table, k_scale, v_scale)
+    paged = block_table is not None
 
     ext = dispatch(q)
-    kernel = (ext is not None
-              and q.dtype in (torch.float16, torch.bfloat16)
-              and q.shape[-1] in (64, 128)
-              and (block_table is None
-                   or _paged_kernel_page_size(k_cache.shape[1])))
-    if kernel:
-        ql = q_lens.contiguous() if q_lens is not None else _NO_LENS
-        args = [q.contiguous(), k_cache, v_cache, lens.contiguous(), ql]
-        if block_table is not None:
-            args.append(block_table.contiguous())
-        if fp8:
-            args += [k_scale, v_scale]
-        name = ("fa_kvcache_mq" + ("_paged" if block_table is not None else "")
-                + ("_fp8" if fp8 else ""))
-        out, lse = getattr(ext, name)(*args, softmax_scale, wl)
+    if ext is not None and covered:
+        out, lse = ext.fa_kvcache_mq(
+            q.contiguous(), k_cache, v_cache, lens.contiguous(),
+            q_lens.contiguous() if q_lens is not None else _ABSENT,
+            block_table.contiguous() if paged else _ABSENT,
+            k_scale if fp8 else _ABSENT, v_scale if fp8 else _ABSENT,
+            softmax_scale, wl)
     else:
         if ext is not None:
             key = (q.dtype, q.shape[-1],
-                   k_cache.shape[1] if block_table is not None else None, fp8)
+                   k_cache.shape[1] if paged else None, fp8)
             if key not in _warned_chunk:
                 _warned_chunk.add(key)
                 from ..utils.logger import logger
@@ -1197,7 +1119,7 @@ def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
                     "page_size %s / fp8 %s is not covered by the HIP kernel; "
                     "running the fp32 composite on a copy of the cache on "
                     "the device", *key)
-        if block_table is not None:
+        if paged:
             k_cache = _gather_pages(k_cache, block_table)
             v_cache = _gather_pages(v_cache, block_table)
         if fp8:
