@@ -77,12 +77,15 @@ std::vector<torch::Tensor> fa_decode(torch::Tensor q, torch::Tensor k_cache,
                                      long num_splits);
 
 // flash_attn_kvcache_mq.hip; q_lens / block_table / k_scale / v_scale: empty
-// 1-d = absent
+// 1-d = absent; num_splits: 0 = chosen from the shapes, 1 = unsplit
 std::vector<torch::Tensor> fa_kvcache_mq(
     torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
     torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
-    long wl);
+    long wl, long num_splits);
+long fa_kvcache_mq_num_splits(long b, long hk, long packed_rows, long cap,
+                              long num_cus);
+std::vector<long> fa_kvcache_mq_split_constants();
 
 // kv_cache_write.hip
 void kv_cache_write_fp8(torch::Tensor k, torch::Tensor v,
@@ -118,6 +121,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_varlen_backward", &fa_varlen_backward);
   m.def("fa_decode", &fa_decode);
   m.def("fa_kvcache_mq", &fa_kvcache_mq);
+  m.def("fa_kvcache_mq_num_splits", &fa_kvcache_mq_num_splits);
+  m.def("fa_kvcache_mq_split_constants", &fa_kvcache_mq_split_constants);
   m.def("kv_cache_write_fp8", &kv_cache_write_fp8);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);
   m.def("lt_gemm", &lt_gemm, pybind11::arg("a"), pybind11::arg("b"),

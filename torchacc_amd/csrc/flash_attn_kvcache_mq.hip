@@ -19,8 +19,8 @@
 //     sq = 4..16 at rep = 4..8 already fills 32-row MFMA tiles. The lane's row
 //     gives j = m / rep for the mask and h = kh * rep + m % rep for the Q
 //     load and the O / LSE store.
-//   - Row tile = 4 waves x 32 rows = 128 packed rows (256 threads). There is
-//     no split over the keys, so the row tiles are the only parallelism
+//   - Row tile = 4 waves x 32 rows = 128 packed rows (256 threads). Without
+//     SPLIT (below) the row tiles are the only parallelism
 //     inside one (sequence, kv head): 128 rows give twice the workgroups of
 //     fa_fwd's 256, and the staging registers of a 64-key tile (8 x 16 bytes
 //     per thread at d = 128) still fit without scratch.
@@ -46,8 +46,22 @@
 //     folded into the factor that scales the scores; v_scale[kh] multiplies
 //     the normalised row once in the epilogue. Both are read from device
 //     memory.
+//   - SPLIT (compile-time): split-KV, the decode kernel's cut applied per
+//     workgroup. The grid's x dimension carries (row tile, split); a workgroup
+//     computes its own tile range [t0, t1) as above, then takes tps =
+//     ceil(ntiles / num_splits) tiles starting at t0 + split * tps. The key
+//     range that loads clamp into, and that stage_write zeroes outside of,
+//     is the intersection of the split's tiles with [kv_lo, kv_hi), so the
+//     guarantees about invisible slots and table entries hold per split. The
+//     epilogue writes fp32 partials (normalised row, v_scale applied, and the
+//     split's lse; -inf for every row the split holds no visible key of, whose
+//     row of o_part stays unwritten), and fa_kvcache_mq_combine_kernel forms
+//     the fixed-order log-sum-exp weighted sum per (b, j, h) row. The
+//     workspace is never initialised: the combine reads an o_part row only
+//     behind a finite lse. SPLIT = false is the kernel without any of this;
+//     it receives an empty MqSplit and reads none of it.
 // Plain vector stores only, no atomics, one fixed reduction order: the result
-// is deterministic.
+// is deterministic for a given num_splits.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <type_traits>
@@ -91,9 +105,25 @@ DEVINLINE s16x8 mq_cvt8_fp8(const u32x2& r) {
   return out;
 }
 
+// Split-KV arguments. Empty without SPLIT, so those instances receive no
+// workspace pointers (as DecScales<FP8> in flash_attn_decode.hip).
+//   o_part   [b, sq, hq, num_splits, d]  fp32, normalised rows
+//   lse_part [b, sq, hq, num_splits]     fp32
+// Both are indexed by the row of O, (b * sq + j) * hq + h: the combine reads
+// the num_splits lse values and rows of one output row back to back.
+template <bool SPLIT>
+struct MqSplit {};
+
+template <>
+struct MqSplit<true> {
+  float* o_part;
+  float* lse_part;
+  int num_splits;
+};
+
 // In HIP the second launch-bounds argument is waves per SIMD: 2 gives a
 // 256-VGPR budget (the 64 KB of LDS at d = 128 admit 2 workgroups per CU).
-template <int D, bool FP16, bool PAGED, bool FP8>
+template <int D, bool FP16, bool PAGED, bool FP8, bool SPLIT>
 __global__ __launch_bounds__(MQ_THREADS, 2)
 void fa_kvcache_mq_kernel(const short* __restrict__ Q,
                           const void* __restrict__ Kp,
@@ -109,7 +139,8 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
                           const int* __restrict__ block_table,
                           int page_shift, int num_pages,
                           const float* __restrict__ k_scale,
-                          const float* __restrict__ v_scale) {
+                          const float* __restrict__ v_scale,
+                          MqSplit<SPLIT> sp) {
   using ET = AttnElem<FP16>;
   using KE = typename std::conditional<FP8, unsigned char, short>::type;
   using KV8 = typename std::conditional<FP8, u32x2, s16x8>::type;
@@ -136,7 +167,15 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
   const int M = sq * rep;            // packed rows of one (sequence, kv head)
   const int kh = blockIdx.y;
   const int b = blockIdx.z;
-  const int m0wg = blockIdx.x * MQ_ROWS;
+  // SPLIT: blockIdx.x = row tile * num_splits + split
+  int m0wg_x = blockIdx.x * MQ_ROWS;
+  int split = 0;
+  if constexpr (SPLIT) {
+    const int row_tile = blockIdx.x / sp.num_splits;
+    split = blockIdx.x - row_tile * sp.num_splits;
+    m0wg_x = row_tile * MQ_ROWS;
+  }
+  const int m0wg = m0wg_x;
   const int m0 = m0wg + wid * 32;    // this wave's first packed row
   const int mrow = m0 + col;         // this lane's packed row
 
@@ -156,11 +195,24 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
   // ---- workgroup key range: union of the rows' visible ranges ------------
   const int jf_wg = m0wg / rep;
   const int jl_wg = min(n - 1, min(M - 1, m0wg + MQ_ROWS - 1) / rep);
-  const int kv_hi = min(L, max(0, shift + jl_wg + 1));           // exclusive
-  const int kv_lo = (wl >= 0) ? max(0, max(shift + jf_wg, 0) - wl) : 0;
-  const int t0 = kv_lo / KVB;
+  int kv_hi = min(L, max(0, shift + jl_wg + 1));                 // exclusive
+  int kv_lo = (wl >= 0) ? max(0, max(shift + jf_wg, 0) - wl) : 0;
+  int t0 = kv_lo / KVB;
   const int t1 = (kv_hi + KVB - 1) / KVB;                        // exclusive
-  const int ntiles = (jf_wg < n && kv_hi > kv_lo) ? t1 - t0 : 0;
+  int ntiles = (jf_wg < n && kv_hi > kv_lo) ? t1 - t0 : 0;
+  if constexpr (SPLIT) {
+    // this split's tiles [tb, te) of the workgroup's own range, and the key
+    // range narrowed to them. With ntiles > 0 afterwards, t0 <= tb < te <= t1
+    // gives max(kv_lo, tb * KVB) < min(kv_hi, te * KVB): the clamp of src_key
+    // stays inside the split and inside [kv_lo, kv_hi).
+    const int tps = (ntiles + sp.num_splits - 1) / sp.num_splits;
+    const int tb = t0 + split * tps;
+    const int te = min(t0 + ntiles, tb + tps);
+    ntiles = max(te - tb, 0);
+    t0 = tb;
+    kv_lo = max(kv_lo, tb * KVB);
+    kv_hi = min(kv_hi, te * KVB);
+  }
 
   // ---- this wave's rows ---------------------------------------------------
   const int jf_w = m0 / rep;
@@ -404,7 +456,35 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
   }
 
   // ---- epilogue: every row m < M is written -------------------------------
-  if (in_range) {
+  if constexpr (SPLIT) {
+    // fp32 partials. Every row gets its lse (-inf: the split is empty for the
+    // workgroup, the wave or the row); only rows with a visible key in this
+    // split write their normalised row, with 16-byte stores.
+    if (in_range) {
+      const long prow_idx =
+          (((long)(b * (long)sq + jr) * hq + h) * sp.num_splits + split);
+      if (l_run > 0.f) {
+        float inv_l = 1.f / l_run;
+        if constexpr (FP8) inv_l *= v_scale[kh];   // once per normalised row
+        float* op = sp.o_part + prow_idx * D;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            // registers 4g..4g+3 are d = a*32 + 8g + 4hi + 0..3
+            f32x4 w;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) w[e] = oacc[a][4 * g + e] * inv_l;
+            *reinterpret_cast<f32x4*>(op + a * 32 + CROW(4 * g, hi)) = w;
+          }
+        }
+      }
+      if (hi == 0) {
+        sp.lse_part[prow_idx] =
+            (l_run > 0.f) ? m_run + __logf(l_run) : -INFINITY;
+      }
+    }
+  } else if (in_range) {
     float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
     if constexpr (FP8) inv_l *= v_scale[kh];   // once per normalised row
     short* op = O + ((long)(b * (long)sq + jr) * hq + h) * D;
@@ -431,26 +511,121 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
 // host side
 // ---------------------------------------------------------------------------
 
+// Split-KV combine: one fixed-order log-sum-exp weighted sum of the
+// normalised partials per output row (b, j, h). D / 4 adjacent lanes serve a
+// row, 4 head-dim elements each (16-byte loads, one 8-byte store); a 256-thread
+// workgroup serves 1024 / D rows. A split whose lse is -inf is skipped without
+// reading its (possibly never written) partial row.
+constexpr int MQ_COMBINE_THREADS = 256;
+
+template <int D, bool FP16>
+__global__ __launch_bounds__(MQ_COMBINE_THREADS)
+void fa_kvcache_mq_combine_kernel(const float* __restrict__ o_part,
+                                  const float* __restrict__ lse_part,
+                                  short* __restrict__ O,
+                                  float* __restrict__ LSE, long rows, int sq,
+                                  int hq, int num_splits) {
+  using ET = AttnElem<FP16>;
+  constexpr int LPR = D / 4;                     // lanes per row
+  constexpr int RPB = MQ_COMBINE_THREADS / LPR;  // rows per workgroup
+  const long row = (long)blockIdx.x * RPB + threadIdx.x / LPR;
+  if (row >= rows) return;
+  const int d = (threadIdx.x % LPR) * 4;
+  const float* lp = lse_part + row * num_splits;
+  float mx = -INFINITY;
+  for (int s = 0; s < num_splits; ++s) mx = fmaxf(mx, lp[s]);
+  float wsum = 0.f;
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (mx != -INFINITY) {  // otherwise -inf - -inf
+    for (int s = 0; s < num_splits; ++s) {
+      const float ls = lp[s];
+      if (ls != -INFINITY) {
+        const float w = __expf(ls - mx);
+        wsum += w;
+        const f32x4 p = *reinterpret_cast<const f32x4*>(
+            o_part + (row * num_splits + s) * D + d);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] += w * p[e];
+      }
+    }
+  }
+  const float inv = wsum > 0.f ? 1.f / wsum : 0.f;
+  s16x4 w;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) w[e] = ET::from_f32(o[e] * inv);
+  *reinterpret_cast<s16x4*>(O + row * D + d) = w;
+  if (d == 0) {
+    // row = (b * sq + j) * hq + h -> LSE[b, h, j]
+    const long bj = row / hq;
+    const int h = (int)(row - bj * hq);
+    const long bb = bj / sq;
+    const int j = (int)(bj - bb * sq);
+    LSE[(bb * hq + h) * sq + j] =
+        wsum > 0.f ? mx + __logf(wsum) : -INFINITY;
+  }
+}
+
+// Host-side split choice, from shapes and the CU count alone (no device data,
+// no sync, safe under graph capture; the tiles are cut on the device). Aim
+// for ~2 workgroups per CU over b * hk * row_tiles. A split must be able to
+// own MQ_MIN_KEYS_PER_SPLIT slots of the cache: one that owns fewer than 8
+// tiles reads at most 8 x 32 KB of K/V at d = 128 while it may write 64 KB of
+// partials, so the floor is at least 512 whatever the timing says, and the
+// choice is 1 for every cap < 2 * floor. MQ_MAX_SPLITS bounds the automatic
+// choice (workspace, combine loop); MQ_SPLIT_LIMIT bounds a forced count.
+// Values and the rows that decided them: profiles/r11_kvcache_chunk_split.md.
+constexpr long MQ_MIN_KEYS_PER_SPLIT = 512;
+constexpr long MQ_MAX_SPLITS = 32;
+constexpr long MQ_SPLIT_LIMIT = 128;
+
+long mq_choose_num_splits(long b, long hk, long packed_rows, long cap,
+                          long num_cus) {
+  const long row_tiles = (packed_rows + MQ_ROWS - 1) / MQ_ROWS;
+  const long base = std::max<long>(b * hk * row_tiles, 1);
+  long s = (2 * num_cus) / base;
+  s = std::min(s, cap / MQ_MIN_KEYS_PER_SPLIT);
+  s = std::min(s, MQ_MAX_SPLITS);
+  return std::max<long>(s, 1);
+}
+
+// ns == 1: the unsplit instance writes O / LSE, sp_o / sp_lse are unused.
+// ns > 1: the split instance writes the partials, then the combine.
 template <int D, bool FP16, bool PAGED, bool FP8>
 void mq_launch(const torch::Tensor& q, const torch::Tensor& k,
                const torch::Tensor& v, const int* klp, const int* qlp,
                torch::Tensor& o, torch::Tensor& lse, int cap, float scale,
                int wl, const int* bt, int page_shift, const float* k_scale,
-               const float* v_scale, hipStream_t stream) {
+               const float* v_scale, int ns, float* o_part, float* lse_part,
+               hipStream_t stream) {
   const int b = q.size(0), sq = q.size(1), hq = q.size(2);
   const int hk = k.size(2);
   const int rows = sq * (hq / hk);
-  dim3 grid((rows + MQ_ROWS - 1) / MQ_ROWS, hk, b);
+  const int row_tiles = (rows + MQ_ROWS - 1) / MQ_ROWS;
   const int lds = 4 * MQ_KVB * D * 2;  // K + V^T, double buffered
-  hipLaunchKernelGGL((fa_kvcache_mq_kernel<D, FP16, PAGED, FP8>), grid,
-                     dim3(MQ_THREADS), lds, stream,
-                     (const short*)q.data_ptr(), (const void*)k.data_ptr(),
-                     (const void*)v.data_ptr(), klp, qlp,
-                     (short*)o.data_ptr(), lse.data_ptr<float>(), sq, cap,
-                     hq, hk, (long)k.stride(0), (long)k.stride(1),
-                     (long)v.stride(0), (long)v.stride(1), scale, wl, bt,
-                     page_shift, PAGED ? (int)k.size(0) : 0, k_scale,
-                     v_scale);
+#define MQ_KERNEL_ARGS                                                       \
+  (const short*)q.data_ptr(), (const void*)k.data_ptr(),                     \
+      (const void*)v.data_ptr(), klp, qlp, (short*)o.data_ptr(),             \
+      lse.data_ptr<float>(), sq, cap, hq, hk, (long)k.stride(0),             \
+      (long)k.stride(1), (long)v.stride(0), (long)v.stride(1), scale, wl,    \
+      bt, page_shift, PAGED ? (int)k.size(0) : 0, k_scale, v_scale
+  if (ns == 1) {
+    hipLaunchKernelGGL((fa_kvcache_mq_kernel<D, FP16, PAGED, FP8, false>),
+                       dim3(row_tiles, hk, b), dim3(MQ_THREADS), lds, stream,
+                       MQ_KERNEL_ARGS, MqSplit<false>{});
+    return;
+  }
+  hipLaunchKernelGGL((fa_kvcache_mq_kernel<D, FP16, PAGED, FP8, true>),
+                     dim3(row_tiles * ns, hk, b), dim3(MQ_THREADS), lds,
+                     stream, MQ_KERNEL_ARGS,
+                     MqSplit<true>{o_part, lse_part, ns});
+#undef MQ_KERNEL_ARGS
+  constexpr int RPB = MQ_COMBINE_THREADS / (D / 4);
+  const long out_rows = (long)b * sq * hq;
+  hipLaunchKernelGGL((fa_kvcache_mq_combine_kernel<D, FP16>),
+                     dim3((unsigned)((out_rows + RPB - 1) / RPB)),
+                     dim3(MQ_COMBINE_THREADS), 0, stream, o_part, lse_part,
+                     (short*)o.data_ptr(), lse.data_ptr<float>(), out_rows,
+                     sq, hq, ns);
 }
 
 constexpr const char* MQ_OP = "fa_kvcache_mq";
@@ -465,7 +640,8 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
                                   const torch::Tensor& block_table,
                                   const torch::Tensor& k_scale,
                                   const torch::Tensor& v_scale,
-                                  double softmax_scale, long wl) {
+                                  double softmax_scale, long wl,
+                                  long num_splits) {
   TORCH_CHECK(q.is_cuda() && q.dim() == 4 && q.is_contiguous(),
               "fa_kvcache_mq: q must be a contiguous GPU [b, sq, hq, d]");
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 ||
@@ -495,15 +671,41 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
   }
   wl = std::min<long>(wl, 1L << 30);  // anything larger is "no window"
 
+  TORCH_CHECK(num_splits >= 0 && num_splits <= MQ_SPLIT_LIMIT,
+              "fa_kvcache_mq: num_splits must be in [0, ", MQ_SPLIT_LIMIT,
+              "] (0: chosen from the shapes, 1: no split), got ", num_splits);
+  const long packed_rows = sq * (hq / hk);
+  long ns = num_splits;
+  if (ns == 0)
+    ns = mq_choose_num_splits(
+        b, hk, packed_rows, geo.cap,
+        at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  if (ns > 1) {
+    // grid x carries (row tile, split); the combine serves >= 8 rows per
+    // workgroup. Both stay below 2^24 workgroups of 256 threads.
+    const long row_tiles = (packed_rows + MQ_ROWS - 1) / MQ_ROWS;
+    TORCH_CHECK(row_tiles * ns <= (1L << 23) && b * sq * hq <= (1L << 26),
+                "fa_kvcache_mq: too many rows for num_splits = ", ns,
+                "; use num_splits = 1");
+  }
+
   auto o = torch::empty_like(q);
   auto lse = torch::empty({b, hq, sq}, q.options().dtype(torch::kFloat32));
+  torch::Tensor o_part, lse_part;  // no memset: see the kernels
+  float *opp = nullptr, *lpp = nullptr;
+  if (ns > 1) {
+    o_part = torch::empty({b, sq, hq, ns, D}, lse.options());
+    lse_part = torch::empty({b, sq, hq, ns}, lse.options());
+    opp = o_part.data_ptr<float>();
+    lpp = lse_part.data_ptr<float>();
+  }
   auto stream = at::hip::getCurrentHIPStream();
 #define MQ_LAUNCH(DD)                                                        \
   FP16_SWITCH(q.scalar_type() == torch::kHalf,                               \
               mq_launch<DD, kFP16, PAGED, FP8>(                              \
                   q, k_cache, v_cache, klp, qlp, o, lse, (int)geo.cap,       \
                   (float)softmax_scale, (int)wl, geo.table, geo.page_shift,  \
-                  ks, vs, stream))
+                  ks, vs, (int)ns, opp, lpp, stream))
   if (D == 128) MQ_LAUNCH(128); else MQ_LAUNCH(64);
 #undef MQ_LAUNCH
   HIP_CHECK_LAST();
@@ -516,12 +718,14 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
 // empty 1-d tensor means absent. With a table the caches are page pools
 // [num_pages, page_size, hk, d]. With scales (fp32 [hk] on the device, both
 // or neither) they hold float8_e4m3fn codes: score = softmax_scale *
-// k_scale[kh] * (q . K8), out = v_scale[kh] * sum p V8.
+// k_scale[kh] * (q . K8), out = v_scale[kh] * sum p V8. num_splits: 0 lets
+// the host choose the number of key splits from the shapes, 1 runs the
+// unsplit kernel, 2..MQ_SPLIT_LIMIT (128) forces that count.
 std::vector<torch::Tensor> fa_kvcache_mq(
     torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
     torch::Tensor k_lens, torch::Tensor q_lens, torch::Tensor block_table,
     torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
-    long wl) {
+    long wl, long num_splits) {
   const bool fp8 = kvc_present(k_scale);
   TORCH_CHECK(fp8 == kvc_present(v_scale),
               "fa_kvcache_mq: k_scale and v_scale come together");
@@ -529,5 +733,19 @@ std::vector<torch::Tensor> fa_kvcache_mq(
                  ? (fp8 ? mq_run<true, true> : mq_run<true, false>)
                  : (fp8 ? mq_run<false, true> : mq_run<false, false>);
   return run(q, k_cache, v_cache, k_lens, q_lens, block_table, k_scale,
-             v_scale, softmax_scale, wl);
+             v_scale, softmax_scale, wl, num_splits);
+}
+
+// The automatic choice as a pure function of the shapes (tests, benchmarks).
+long fa_kvcache_mq_num_splits(long b, long hk, long packed_rows, long cap,
+                              long num_cus) {
+  TORCH_CHECK(b >= 1 && hk >= 1 && packed_rows >= 1 && cap >= 1 &&
+                  num_cus >= 1,
+              "fa_kvcache_mq_num_splits: every argument must be >= 1");
+  return mq_choose_num_splits(b, hk, packed_rows, cap, num_cus);
+}
+
+// {MQ_MIN_KEYS_PER_SPLIT, MQ_MAX_SPLITS, MQ_SPLIT_LIMIT}
+std::vector<long> fa_kvcache_mq_split_constants() {
+  return {MQ_MIN_KEYS_PER_SPLIT, MQ_MAX_SPLITS, MQ_SPLIT_LIMIT};
 }

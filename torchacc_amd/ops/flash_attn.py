@@ -1050,7 +1050,7 @@ def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
                                   q_seqlens=None, softmax_scale=None,
                                   window_size=(-1, -1), return_lse=False,
                                   block_table=None, k_scale=None,
-                                  v_scale=None):
+                                  v_scale=None, num_splits=0):
     """Attention of several new tokens per sequence over a KV cache,
     inference only: chunked prefill, a shared cached prefix, speculative
     verification (k draft tokens against the cache), mixed prefill / decode
@@ -1082,15 +1082,29 @@ def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
     bf16/fp16 q with d in {64, 128} on the GPU (and, paged, a page size that
     is a power of two >= 16) runs the HIP kernel of
     csrc/flash_attn_kvcache_mq.hip: the GQA group is packed into the MFMA row
-    dimension, so K and V are read once per kv head. It is deterministic,
-    and the paged result is bitwise the contiguous one on the gathered cache.
-    It does not split the keys: one short chunk against a very long context
-    at batch 1 uses few workgroups. Other GPU inputs (fp32 q, other head
-    dims, other page sizes) gather / dequantise a copy on the device and run
-    an fp32 composite there, still without a host sync. Returns out [b, sq,
-    hq, d], and lse [b, hq, sq] (fp32, natural log) with ``return_lse``."""
+    dimension, so K and V are read once per kv head. ``num_splits`` (a
+    non-negative int) says into how many pieces the kernel cuts the keys of
+    every (sequence, kv head, 128-row tile), each piece on a workgroup of its
+    own, with a second launch that combines the fp32 partial results: 0 lets
+    the host choose from the shapes and the CU count alone (1 for every cap
+    below 1024, and whenever the row tiles already fill the device), 1 runs
+    the unsplit kernel, N in 2..128 forces N pieces (a short chunk against a
+    long context at a small batch is the case that gains). The pieces are
+    cut on the device from the lengths, so no value of ``num_splits`` adds a
+    host sync, and a captured graph follows new lengths. The result is
+    deterministic for a given ``num_splits`` (different values differ in
+    the last bits), and the paged result is bitwise the contiguous one on
+    the gathered cache at the same ``num_splits``. Other GPU inputs (fp32 q,
+    other head dims, other page sizes) gather / dequantise a copy on the
+    device and run an fp32 composite there, still without a host sync; they
+    and the CPU path validate ``num_splits`` and ignore it. Returns out [b,
+    sq, hq, d], and lse [b, hq, sq] (fp32, natural log) with
+    ``return_lse``."""
     assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
         "expected q [b, sq, hq, d] and caches [b, cap, hk, d]"
+    assert (isinstance(num_splits, int) and not isinstance(num_splits, bool)
+            and num_splits >= 0), \
+        f"num_splits must be a non-negative int, got {num_splits!r}"
     assert q.shape[1] >= 1, "q needs at least one row per sequence"
     assert isinstance(cache_seqlens, torch.Tensor), \
         "flash_attn_chunk_with_kvcache requires cache_seqlens"
@@ -1106,7 +1120,7 @@ def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
             q_lens.contiguous() if q_lens is not None else _ABSENT,
             block_table.contiguous() if paged else _ABSENT,
             k_scale if fp8 else _ABSENT, v_scale if fp8 else _ABSENT,
-            softmax_scale, wl)
+            softmax_scale, wl, num_splits)
     else:
         if ext is not None:
             key = (q.dtype, q.shape[-1],
