@@ -25,6 +25,7 @@ sources = [
         "flash_attn_decode.hip",
         "flash_attn_kvcache_mq.hip",
         "kv_cache_write.hip",
+        "rope_kv_write.hip",
         "flash_attn_extra_fwd.hip",
         "flash_attn_extra_bwd.hip",
         "gemm.hip",

@@ -93,6 +93,15 @@ void kv_cache_write_fp8(torch::Tensor k, torch::Tensor v,
                         torch::Tensor slots, torch::Tensor k_scale,
                         torch::Tensor v_scale);
 
+// rope_kv_write.hip; k_scale / v_scale: empty 1-d = absent (16-bit caches)
+torch::Tensor rope_kv_cache_write(torch::Tensor q, torch::Tensor k,
+                                  torch::Tensor v, torch::Tensor cos,
+                                  torch::Tensor sin, torch::Tensor positions,
+                                  torch::Tensor k_cache,
+                                  torch::Tensor v_cache, torch::Tensor slots,
+                                  torch::Tensor k_scale,
+                                  torch::Tensor v_scale);
+
 // gemm.hip (hipBLASLt tuned GEMM)
 std::vector<int64_t> lt_gemm_candidates(int64_t m, int64_t n, int64_t k,
                                         bool ta, bool tb,
@@ -124,6 +133,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_kvcache_mq_num_splits", &fa_kvcache_mq_num_splits);
   m.def("fa_kvcache_mq_split_constants", &fa_kvcache_mq_split_constants);
   m.def("kv_cache_write_fp8", &kv_cache_write_fp8);
+  m.def("rope_kv_cache_write", &rope_kv_cache_write);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);
   m.def("lt_gemm", &lt_gemm, pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("ta"), pybind11::arg("tb"),

@@ -21,9 +21,9 @@ by one block table that all layers share. The decode kernel's paged variant
 differs from the contiguous one in its address computation only. A fresh
 prefill attends the prompt's own K/V and scatters them into the pages;
 several new tokens against a non-empty paged or fp8 cache (``prefill_chunk``)
-run ``flash_attn_chunk_with_kvcache``, which reads the cache in place. Not
-covered: a continuous-batching scheduler, ragged prompts and prefix-cache
-management.
+run ``flash_attn_chunk_with_kvcache``, which reads the cache in place.
+Ragged prompts and continuous batching live in ``models/serving.py``; not
+covered: prefix-cache management.
 
 With ``kv_dtype="fp8"`` either cache stores OCP e4m3fn codes (one byte per
 element, half the pool and half the bytes a decode step reads) with one fp32
@@ -249,6 +249,19 @@ class PagedKVCache:
         page = self.table.gather(1, (positions >> self.shift)).long()
         return (page * self.page_size
                 + (positions & (self.page_size - 1))).reshape(-1)
+
+    def slot_indices_ragged(self, positions: torch.Tensor) -> torch.Tensor:
+        """``slot_indices`` for a ragged step: positions [b, s] (device,
+        int32 or int64) with -1 for padding -> flat slots [b * s] (int64),
+        -1 where the position is negative (or past the table's capacity).
+        The position is clamped before the table lookup, so padding
+        dereferences nothing. Pure device arithmetic; captures into a
+        graph."""
+        positions = positions.long()
+        cap = self.table_width * self.page_size
+        slots = self.slot_indices(positions.clamp(0, cap - 1))
+        pad = (positions < 0) | (positions >= cap)
+        return torch.where(pad.reshape(-1), torch.full_like(slots, -1), slots)
 
     def begin_step(self, positions: torch.Tensor):
         """Compute the slots the step's tokens are written to, once for all

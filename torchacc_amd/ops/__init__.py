@@ -5,7 +5,7 @@ from .flash_attn import (  # noqa: F401
     flash_attn_varlen_func, flash_attn_varlen_position_ids_xla,
     flash_attn_varlen_qkvpacked_xla, flash_attn_varlen_xla,
     flash_attn_with_kvcache, flash_attn_xla, kv_cache_write_fp8,
-    spmd_flash_attn_varlen_xla)
+    rope_kv_cache_write, spmd_flash_attn_varlen_xla)
 from .rmsnorm import RMSNorm, rms_norm  # noqa: F401
 from .rope import apply_rotary_pos_emb, build_rope_cache  # noqa: F401
 from .swiglu import swiglu  # noqa: F401

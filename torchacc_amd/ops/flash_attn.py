@@ -748,6 +748,112 @@ def kv_cache_write_fp8(k, v, k_cache, v_cache, slots, k_scale, v_scale):
         cache.view(torch.uint8)[t // n1, t % n1] = codes.view(torch.uint8)
 
 
+def _rkw_check(cond, msg):
+    if not cond:
+        raise ValueError(f"rope_kv_cache_write: {msg}")
+
+
+def rope_kv_cache_write(q, k, v, cos, sin, positions, k_cache, v_cache, slots,
+                        k_scale=None, v_scale=None):
+    """RoPE at per-token positions, with K and V written straight into the
+    cache; returns the rotated q [b, s, hq, d].
+
+    q [b, s, hq, d], k / v [b, s, hk, d] (bf16/fp16 on the GPU; [heads, d]
+    dense, d % 16 == 0, batch and token strides multiples of 8 elements, so
+    column slices of one fused qkv buffer qualify). cos / sin: the model's
+    FULL fp32 tables [P, d / 2], contiguous, not a slice. ``positions`` and
+    ``slots`` (int32/int64 [b * s], same device) are read on the device:
+    no host sync, and a captured launch follows their values at replay.
+    k_cache / v_cache [n0, n1, hk, d] as in ``kv_cache_write_fp8`` (a
+    contiguous cache or a page pool, flat slot ``t -> [t // n1, t % n1]``),
+    either of q's dtype (then no scales) or float8_e4m3fn with fp32 [hk]
+    ``k_scale`` / ``v_scale``.
+
+    Token t with ``p = positions[t]`` outside [0, P) is padding: its q_rot
+    rows are zero and nothing is written. Otherwise q_rot[t] is q[t] rotated
+    by table row p, and if ``slots[t]`` lies in [0, n0 * n1) that slot
+    receives the rotated k[t] and v[t]. Duplicate slots are unspecified.
+
+    Bitwise equal to ``apply_rotary_pos_emb`` (with the rows' table slices)
+    followed by ``index_copy_`` or ``kv_cache_write_fp8``: the rotation is
+    computed in fp32 and rounded once to the element type; an fp8 cache
+    quantises that rounded value. One HIP launch (csrc/rope_kv_write.hip),
+    no workspace, no autograd. CPU and fp32 tensors take a torch reference
+    with the same semantics."""
+    _rkw_check(q.dim() == 4 and k.dim() == 4 and v.shape == k.shape
+               and q.shape[:2] == k.shape[:2] and q.shape[3] == k.shape[3],
+               "q [b, s, hq, d] and k, v [b, s, hk, d] disagree")
+    _rkw_check(q.dtype == k.dtype == v.dtype, "q, k and v must share a dtype")
+    b, s, hq, d = q.shape
+    hk = k.shape[2]
+    _rkw_check(d % 16 == 0, "head_dim must be a multiple of 16")
+    _rkw_check(cos.dim() == 2 and cos.shape == sin.shape
+               and cos.shape[1] == d // 2 and cos.shape[0] >= 1
+               and cos.dtype == sin.dtype == torch.float32,
+               "cos and sin must be fp32 [P, d / 2] tables with P >= 1")
+    _rkw_check(k_cache.dim() == 4 and k_cache.shape == v_cache.shape
+               and k_cache.shape[2:] == k.shape[2:],
+               "k_cache and v_cache must be [n0, n1, hk, d]")
+    _rkw_check(k_cache.dtype == v_cache.dtype
+               and k_cache.dtype in (k.dtype, FP8_DTYPE),
+               "the caches must have k's dtype or be float8_e4m3fn")
+    fp8 = k_cache.dtype == FP8_DTYPE
+    for name, t in (("positions", positions), ("slots", slots)):
+        _rkw_check(t.dtype in (torch.int32, torch.int64)
+                   and t.shape == (b * s,),
+                   f"{name} must be int32 or int64 [b * s]")
+    for name, t in (("k", k), ("v", v), ("cos", cos), ("sin", sin),
+                    ("positions", positions), ("slots", slots),
+                    ("k_cache", k_cache), ("v_cache", v_cache),
+                    ("k_scale", k_scale), ("v_scale", v_scale)):
+        _rkw_check(t is None or t.device == q.device,
+                   f"{name} must live on q's device")
+    if fp8:
+        _rkw_check(k_scale is not None and v_scale is not None,
+                   "float8_e4m3fn caches need k_scale and v_scale")
+        _check_kv_scale(k_scale, k_cache, "k_scale")
+        _check_kv_scale(v_scale, v_cache, "v_scale")
+    else:
+        _rkw_check(k_scale is None and v_scale is None,
+                   "k_scale / v_scale apply to float8_e4m3fn caches only")
+    ext = dispatch(q)
+    if ext is not None and q.dtype in (torch.bfloat16, torch.float16):
+        if slots.dtype != positions.dtype:
+            slots = slots.to(positions.dtype)
+        return ext.rope_kv_cache_write(
+            q, k, v, cos, sin, positions.contiguous(), k_cache, v_cache,
+            slots.contiguous(), k_scale if fp8 else _ABSENT,
+            v_scale if fp8 else _ABSENT)
+    P, d2 = cos.shape[0], d // 2
+    pos = positions.long()
+    real = (pos >= 0) & (pos < P)
+    row = pos.clamp(0, P - 1)
+    c = cos[row].view(b, s, 1, d2)
+    sn = sin[row].view(b, s, 1, d2)
+
+    def rot(x):
+        x1, x2 = x[..., :d2].float(), x[..., d2:].float()
+        return torch.cat([x1 * c - x2 * sn, x2 * c + x1 * sn],
+                         dim=-1).to(x.dtype)
+
+    q_rot = torch.where(real.view(b, s, 1, 1), rot(q), torch.zeros_like(q))
+    n0, n1 = k_cache.shape[:2]
+    t = slots.long()
+    ok = real & (t >= 0) & (t < n0 * n1)
+    t = t[ok]
+    for x, cache, scale in ((rot(k), k_cache, k_scale),
+                            (v, v_cache, v_scale)):
+        x = x.reshape(-1, hk, d)[ok]
+        if fp8:
+            y = x.float() * (1.0 / scale).view(1, -1, 1)
+            codes = y.clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+            # no float8 index kernels on the CPU: store the bytes
+            cache.view(torch.uint8)[t // n1, t % n1] = codes.view(torch.uint8)
+        else:
+            cache[t // n1, t % n1] = x
+    return q_rot
+
+
 def _decode_fallback_gpu(q, k_cache, v_cache, lens, softmax_scale, wl):
     """GPU inputs the decode kernel does not cover (fp32, head dims other
     than 64/128): the fixed-length attention path on a copy of the cache.
