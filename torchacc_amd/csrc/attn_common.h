@@ -148,6 +148,111 @@ constexpr bool attn_dual_slot_coord_ok() {
 static_assert(attn_dual_slot_coord_ok<64>() && attn_dual_slot_coord_ok<128>(),
               "attn_dual_slot_coord must invert attn_dual_off");
 
+// Workgroup order of the tiled attention kernels (grid = tiles x batch-heads,
+// blockIdx.x fastest). The dispatcher starts blocks in linear order
+// L = blockIdx.y * gridDim.x + blockIdx.x and places block L on XCD L % 8.
+// Under causal masking a workgroup's work grows (or shrinks) monotonically
+// with its tile index, so the blocks are handed out heaviest tile first
+// (longest-processing-time order): the device then drains on light
+// workgroups instead of on a few late-started heavy ones. Batch-heads are
+// taken in chunks of C: inside a chunk L walks the tile ranks, heaviest
+// first, and at each rank the chunk's batch-heads. With C a multiple of 8
+// batch-head j of a full chunk sits on XCD j % 8 with all of its tiles, so
+// its K/V (or Q/dO) stream stays in one L2, and every XCD gets the same mix
+// of heavy and light tiles. The last chunk may be short; nbh <= C is plain
+// heavy-first over the whole grid.
+//   heavy_last = false: tile = rank           (dkv: low kv0 sees most q rows)
+//   heavy_last = true:  tile = tiles-1-rank   (fwd, dq: high q0 sees most keys)
+// Both orders are monotone in weight for any sk - sq shift: q_lo =
+// max(0, kv0 - shift) is non-decreasing in kv0 and a q tile's last visible
+// key is non-decreasing in q0. Only the block -> (tile, batch-head)
+// assignment changes; what a workgroup computes for its tile does not.
+struct AttnWgCoord {
+  int tile;
+  int bh;
+};
+
+template <int C>
+constexpr __host__ __device__ __forceinline__ AttnWgCoord attn_wg_coord(
+    unsigned L, unsigned tiles, unsigned nbh, bool heavy_last) {
+  static_assert(C > 0 && C % 8 == 0,
+                "chunk must keep a batch-head on one XCD (block L -> L % 8)");
+  const unsigned cfull = nbh < (unsigned)C ? nbh : (unsigned)C;
+  const unsigned per = cfull * tiles;          // blocks of a full chunk
+  const unsigned chunk = L / per;
+  const unsigned r = L - chunk * per;
+  const unsigned left = nbh - chunk * cfull;   // batch-heads from this chunk on
+  const unsigned cc = left < cfull ? left : cfull;
+  const unsigned rank = r / cc;
+  return AttnWgCoord{(int)(heavy_last ? tiles - 1 - rank : rank),
+                     (int)(chunk * cfull + (r - rank * cc))};
+}
+
+// compile-time proof over small grids: a bijection onto tiles x nbh, the rank
+// never decreases with L inside a chunk, chunks follow each other, and
+// nbh <= C degenerates to plain heavy-first
+template <int C>
+constexpr bool attn_wg_coord_ok(unsigned tiles, unsigned nbh,
+                                bool heavy_last) {
+  bool seen[32 * 19] = {};
+  if (tiles * nbh > 32 * 19) return false;
+  int prev_chunk = 0, prev_rank = 0;
+  for (unsigned L = 0; L < tiles * nbh; ++L) {
+    const AttnWgCoord c = attn_wg_coord<C>(L, tiles, nbh, heavy_last);
+    if (c.tile < 0 || c.tile >= (int)tiles || c.bh < 0 || c.bh >= (int)nbh)
+      return false;
+    if (seen[c.bh * tiles + c.tile]) return false;
+    seen[c.bh * tiles + c.tile] = true;
+    const int rank = heavy_last ? (int)tiles - 1 - c.tile : c.tile;
+    const int chunk = c.bh / C;
+    if (chunk < prev_chunk) return false;
+    if (chunk == prev_chunk && rank < prev_rank) return false;
+    prev_chunk = chunk;
+    prev_rank = rank;
+    if (nbh <= (unsigned)C &&
+        (rank != (int)(L / nbh) || c.bh != (int)(L % nbh)))
+      return false;
+  }
+  return true;  // tiles * nbh distinct in-range coordinates: onto as well
+}
+template <int C>
+constexpr bool attn_wg_coord_ok_all() {
+  const unsigned tiles[] = {1, 3, 32};
+  const unsigned nbh[] = {1, 5, 8, 19};
+  for (unsigned t : tiles)
+    for (unsigned n : nbh)
+      if (!attn_wg_coord_ok<C>(t, n, false) || !attn_wg_coord_ok<C>(t, n, true))
+        return false;
+  return true;
+}
+static_assert(attn_wg_coord_ok_all<8>() && attn_wg_coord_ok_all<16>() &&
+                  attn_wg_coord_ok_all<64>(),
+              "attn_wg_coord must be a heavy-first bijection onto the grid");
+
+// Chunk of the causal instantiations of fa_fwd, fa_bwd_dkv and fa_bwd_dq,
+// chosen by measurement against 8 and "all batch-heads"
+// (profiles/r13_attn_wg_order.md): 64 keeps the streams of 8 batch-heads per
+// XCD in its L2 and still ends on light tiles.
+constexpr int ATTN_WG_CHUNK = 64;
+
+// This block's (tile, batch-head). Causal kernels take the heavy-first order
+// above. Without causal masking every tile weighs the same and there is no
+// tail to cut, so those instantiations keep the plain order, tile shifted by
+// blockIdx.y so that consecutive blocks (one per XCD) spread evenly.
+template <bool CAUSAL>
+DEVINLINE AttnWgCoord attn_wg_block(bool heavy_last) {
+  if (CAUSAL) {
+    const AttnWgCoord c = attn_wg_coord<ATTN_WG_CHUNK>(
+        blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, heavy_last);
+    // the divisions run on the vector unit; pin the results to scalar
+    // registers (fa_bwd_dkv sits at the 256-VGPR budget)
+    return AttnWgCoord{__builtin_amdgcn_readfirstlane(c.tile),
+                       __builtin_amdgcn_readfirstlane(c.bh)};
+  }
+  return AttnWgCoord{(int)((blockIdx.x + blockIdx.y) % gridDim.x),
+                     (int)blockIdx.y};
+}
+
 // Direct-to-LDS loads (global_load_lds_dwordx4 / _dword): lane l's bytes land
 // at lds_dst + l*16 (or l*4); lds_dst must be wave-uniform. Completion is
 // counted on vmcnt; a barrier after the wait publishes the data.

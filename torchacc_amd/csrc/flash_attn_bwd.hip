@@ -165,11 +165,13 @@ void fa_bwd_dkv_kernel(const short* __restrict__ dOut,
   const int col = lane & 31;
   const int hi = lane >> 5;
 
-  const int kh = blockIdx.y % hk;
-  const int b = blockIdx.y / hk;
+  // heavy-first workgroup order (attn_wg_coord, attn_common.h): under causal
+  // masking the first key tile is seen by the most q rows
+  const AttnWgCoord wg = attn_wg_block<CAUSAL>(false);
+  const int kh = wg.bh % hk;
+  const int b = wg.bh / hk;
   const int gqa = hq / hk;
-  // tile<->XCD decorrelation (see fa_fwd_kernel)
-  const int kv0wg = (int)((blockIdx.x + blockIdx.y) % gridDim.x) * KVWG;
+  const int kv0wg = wg.tile * KVWG;
   const int key_b = kv0wg + wid * 32;          // wave's key block base
   const int mykey = key_b + col;               // lane's key (K frag row)
   const int shift = sk - sq;
@@ -519,11 +521,13 @@ void fa_bwd_dq_kernel(const short* __restrict__ dOut,
   const int col = lane & 31;
   const int hi = lane >> 5;
 
-  const int h = blockIdx.y % hq;
-  const int b = blockIdx.y / hq;
+  // heavy-first workgroup order (attn_wg_coord, attn_common.h): under causal
+  // masking the last q tile sees the most keys
+  const AttnWgCoord wg = attn_wg_block<CAUSAL>(true);
+  const int h = wg.bh % hq;
+  const int b = wg.bh / hq;
   const int kh = h / (hq / hk);
-  // tile<->XCD decorrelation (see fa_fwd_kernel)
-  const int q0wg = (int)((blockIdx.x + blockIdx.y) % gridDim.x) * 256;
+  const int q0wg = wg.tile * 256;
   const int q0 = q0wg + wid * 32;
   const int qrow = q0 + col;
   const int shift = sk - sq;

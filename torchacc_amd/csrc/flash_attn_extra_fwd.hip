@@ -57,15 +57,12 @@ void fa_fwd_kernel_x(const short* __restrict__ Q, const short* __restrict__ K,
   const int col = lane & 31;         // q row within wave block / d col
   const int hi = lane >> 5;          // lane half
 
-  const int h = blockIdx.y % hq;
-  const int b = blockIdx.y / hq;
+  // heavy-first workgroup order (see fa_fwd_kernel)
+  const AttnWgCoord wg = attn_wg_block<CAUSAL>(true);
+  const int h = wg.bh % hq;
+  const int b = wg.bh / hq;
   const int kh = h / (hq / hk);
-  // tile<->XCD decorrelation: the dispatcher places block i on XCD i%8 and
-  // blockIdx.x varies fastest, so with causal tile-skipping a direct
-  // qtile=blockIdx.x maps every heavy (diagonal) workgroup onto the same
-  // XCD; shifting by blockIdx.y balances the causal triangle (bijective
-  // per y-slice)
-  const int q0wg = (int)((blockIdx.x + blockIdx.y) % gridDim.x) * 256;
+  const int q0wg = wg.tile * 256;
   const int q0 = q0wg + wid * 32;        // this wave's q block
   const int qrow = q0 + col;             // this lane's q row
   const int shift = sk - sq;             // bottom-right causal alignment

@@ -50,6 +50,10 @@ void fa_vl_fwd_kernel(const short* __restrict__ Q,
 
   const int h = blockIdx.y;
   const int kh = h / (hq / hk);
+  // plain order, tile shifted by the head (also in the dkv and dq kernels
+  // below): a packed tile's work follows its sequence's bounds (cu_seqlens),
+  // not its index, so the heavy-first order of attn_wg_coord has nothing to
+  // sort by here
   const int q0wg = (int)((blockIdx.x + blockIdx.y) % gridDim.x) * 256;
   const int q0 = q0wg + wid * 32;
   const int qrow = q0 + col;
