@@ -36,6 +36,9 @@ def main():
     p.add_argument("--layers", type=int, default=32)
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--prefill-chunk", type=int, default=64)
+    p.add_argument("--packed", action="store_true",
+                   help="also time ContinuousBatcher(packed=True), "
+                        "alternating with the padded engine")
     args = p.parse_args()
 
     from torchacc_amd.models import (ContinuousBatcher, LlamaForCausalLM,
@@ -55,9 +58,10 @@ def main():
     max_len = max(lens) + NEW
     pages = sum((n + NEW + PAGE - 1) // PAGE for n in lens)
 
-    def engine(reqs):
+    def engine(reqs, packed=False):
         eng = ContinuousBatcher(model, MAX_BATCH, pages, PAGE, max_len,
-                                prefill_chunk=args.prefill_chunk)
+                                prefill_chunk=args.prefill_chunk,
+                                packed=packed)
         rids = [eng.add(r, NEW) for r in reqs]
         outs = eng.run()
         return [outs[r] for r in rids]
@@ -67,6 +71,8 @@ def main():
                                page_size=PAGE)[0].cpu() for r in reqs]
 
     fns = {"engine": engine, "generate": one_by_one}
+    if args.packed:
+        fns["engine_packed"] = lambda reqs: engine(reqs, packed=True)
     for fn in fns.values():
         fn(prompts[:1])
     torch.cuda.synchronize()

@@ -86,6 +86,12 @@ std::vector<torch::Tensor> fa_kvcache_mq(
 long fa_kvcache_mq_num_splits(long b, long hk, long packed_rows, long cap,
                               long num_cus);
 std::vector<long> fa_kvcache_mq_split_constants();
+// packed (cu_seqlens) query layout: q [T, hq, d], cu_q int32 [b + 1]
+std::vector<torch::Tensor> fa_kvcache_varlen(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_lens, torch::Tensor cu_q, torch::Tensor block_table,
+    torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
+    long wl, long num_splits);
 
 // kv_cache_write.hip
 void kv_cache_write_fp8(torch::Tensor k, torch::Tensor v,
@@ -132,6 +138,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_kvcache_mq", &fa_kvcache_mq);
   m.def("fa_kvcache_mq_num_splits", &fa_kvcache_mq_num_splits);
   m.def("fa_kvcache_mq_split_constants", &fa_kvcache_mq_split_constants);
+  m.def("fa_kvcache_varlen", &fa_kvcache_varlen);
   m.def("kv_cache_write_fp8", &kv_cache_write_fp8);
   m.def("rope_kv_cache_write", &rope_kv_cache_write);
   m.def("lt_gemm_candidates", &lt_gemm_candidates);

@@ -60,6 +60,18 @@
 //     workspace is never initialised: the combine reads an o_part row only
 //     behind a finite lse. SPLIT = false is the kernel without any of this;
 //     it receives an empty MqSplit and reads none of it.
+//   - PACKED (compile-time): the cu_seqlens query layout of fa_kvcache_varlen.
+//     q is [T, hq, d]; sequence i owns the rows [cu_q[i], cu_q[i+1]) and
+//     n_i = cu_q[i+1] - cu_q[i] takes the place of q_lens[i]. The grid's x
+//     dimension is a flat list of (sequence, row tile[, split]) work items,
+//     sized on the host from the shapes alone (floor(T * rep / 128) + b row
+//     tiles bound the real count); a workgroup finds its item by a scalar
+//     scan of cu_q and exits when it is past the last one. Everything read
+//     from cu_q is clamped (starts into [0, T], n_i >= 0), so a malformed
+//     cu_q gives wrong numbers, never an out-of-range access. A row tile of
+//     a sequence then runs the ladder below unchanged (M = n_i * rep, shift =
+//     L_i - n_i) and is bitwise the padded instance on that sequence. Rows at
+//     or past cu_q[b] are never written.
 // Plain vector stores only, no atomics, one fixed reduction order: the result
 // is deterministic for a given num_splits.
 #include <torch/extension.h>
@@ -121,26 +133,35 @@ struct MqSplit<true> {
   int num_splits;
 };
 
-// In HIP the second launch-bounds argument is waves per SIMD: 2 gives a
-// 256-VGPR budget (the 64 KB of LDS at d = 128 admit 2 workgroups per CU).
-template <int D, bool FP16, bool PAGED, bool FP8, bool SPLIT>
-__global__ __launch_bounds__(MQ_THREADS, 2)
-void fa_kvcache_mq_kernel(const short* __restrict__ Q,
-                          const void* __restrict__ Kp,
-                          const void* __restrict__ Vp,
-                          const int* __restrict__ k_lens,
-                          const int* __restrict__ q_lens,
-                          short* __restrict__ O, float* __restrict__ LSE,
-                          int sq, int cap, int hq, int hk,
-                          // contiguous: batch / sequence strides; PAGED:
-                          // page / slot strides (elements of the cache)
-                          long k_sb, long k_ss, long v_sb, long v_ss,
-                          float scale, int wl,
-                          const int* __restrict__ block_table,
-                          int page_shift, int num_pages,
-                          const float* __restrict__ k_scale,
-                          const float* __restrict__ v_scale,
-                          MqSplit<SPLIT> sp) {
+// Packed-layout arguments; empty without PACKED, as MqSplit.
+//   cu_q [b + 1]  int32 row offsets into q [T, hq, d]
+template <bool PACKED>
+struct MqPacked {};
+
+template <>
+struct MqPacked<true> {
+  const int* cu_q;
+  int b;
+};
+
+// The kernels' parameters. PACKED: sq is T, the rows of q; q_lens is unused.
+#define MQ_PARAMS                                                            \
+  const short* __restrict__ Q, const void* __restrict__ Kp,                  \
+      const void* __restrict__ Vp, const int* __restrict__ k_lens,           \
+      const int* __restrict__ q_lens, short* __restrict__ O,                 \
+      float* __restrict__ LSE, int sq, int cap, int hq, int hk,              \
+      /* contiguous: batch / sequence strides; PAGED: page / slot strides */ \
+      /* (elements of the cache) */                                          \
+      long k_sb, long k_ss, long v_sb, long v_ss, float scale, int wl,       \
+      const int* __restrict__ block_table, int page_shift, int num_pages,    \
+      const float* __restrict__ k_scale, const float* __restrict__ v_scale
+#define MQ_PASS                                                              \
+  Q, Kp, Vp, k_lens, q_lens, O, LSE, sq, cap, hq, hk, k_sb, k_ss, v_sb,      \
+      v_ss, scale, wl, block_table, page_shift, num_pages, k_scale, v_scale
+
+// The body of the two kernels below (always inlined into them).
+template <int D, bool FP16, bool PAGED, bool FP8, bool SPLIT, bool PACKED>
+DEVINLINE void mq_body(MQ_PARAMS, MqSplit<SPLIT> sp, MqPacked<PACKED> pk) {
   using ET = AttnElem<FP16>;
   using KE = typename std::conditional<FP8, unsigned char, short>::type;
   using KV8 = typename std::conditional<FP8, u32x2, s16x8>::type;
@@ -164,25 +185,49 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
   const int hi = lane >> 5;          // lane half
 
   const int rep = hq / hk;
-  const int M = sq * rep;            // packed rows of one (sequence, kv head)
   const int kh = blockIdx.y;
-  const int b = blockIdx.z;
-  // SPLIT: blockIdx.x = row tile * num_splits + split
-  int m0wg_x = blockIdx.x * MQ_ROWS;
+  // SPLIT: blockIdx.x = row tile * num_splits + split (PACKED: work item
+  // instead of row tile)
+  int row_tile = blockIdx.x;
   int split = 0;
   if constexpr (SPLIT) {
-    const int row_tile = blockIdx.x / sp.num_splits;
+    row_tile = blockIdx.x / sp.num_splits;
     split = blockIdx.x - row_tile * sp.num_splits;
-    m0wg_x = row_tile * MQ_ROWS;
   }
-  const int m0wg = m0wg_x;
+  int b_x = blockIdx.z;
+  int n_x = sq;                      // PACKED: n_i
+  int tok0_x = 0;                    // PACKED: first row of the sequence in q
+  if constexpr (PACKED) {
+    // work item -> (sequence, row tile): scalar scan over the clamped cu_q
+    int item = row_tile, i = 0, start = 0;
+    int end = min(max(pk.cu_q[0], 0), sq);
+    for (;; ++i) {
+      if (i >= pk.b) return;         // past the last item (workgroup-uniform)
+      start = end;
+      end = min(max(pk.cu_q[i + 1], 0), sq);
+      const int ni = max(end - start, 0);
+      const int tiles = (ni * rep + MQ_ROWS - 1) / MQ_ROWS;
+      if (item < tiles) { n_x = ni; break; }
+      item -= tiles;
+    }
+    b_x = i;
+    tok0_x = start;
+    row_tile = item;
+  }
+  const int b = b_x;
+  const int tok0 = tok0_x;
+  const int m0wg = row_tile * MQ_ROWS;
   const int m0 = m0wg + wid * 32;    // this wave's first packed row
   const int mrow = m0 + col;         // this lane's packed row
 
   // ---- per-sequence alignment, from device memory ------------------------
   const int L = min(max(k_lens[b], 0), cap);
-  int n = sq;
-  if (q_lens != nullptr) n = min(max(q_lens[b], 0), sq);
+  int n = n_x;
+  if constexpr (!PACKED) {
+    if (q_lens != nullptr) n = min(max(q_lens[b], 0), sq);
+  }
+  // packed rows of one (sequence, kv head)
+  const int M = (PACKED ? n : sq) * rep;
   const int shift = L - n;
 
   const int jr = mrow / rep;                   // query position of the row
@@ -223,11 +268,16 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
   const bool wave_all = (m0 + 31 < M) && ((m0 + 31) / rep < n) &&
                         (shift + jf_w >= 0);
 
+  // row of q / o: [b, sq] padded, tok0 + j packed
+  const long orow = PACKED ? (long)tok0 + jr : b * (long)sq + jr;
+  const long lse_idx = PACKED ? (long)h * sq + tok0 + jr
+                              : ((long)b * hq + h) * sq + jr;
+
   // ---- Q fragments --------------------------------------------------------
   // B-frag for swapped QK^T: lane holds Q[row][t*16 + hi*8 + j], j=0..7
   bf16x8 qfrag[NT];
   {
-    const long qbase = in_range ? ((long)(b * (long)sq + jr) * hq + h) * D : 0;
+    const long qbase = in_range ? (orow * hq + h) * D : 0;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       s16x8 v = in_range
@@ -461,8 +511,7 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
     // workgroup, the wave or the row); only rows with a visible key in this
     // split write their normalised row, with 16-byte stores.
     if (in_range) {
-      const long prow_idx =
-          (((long)(b * (long)sq + jr) * hq + h) * sp.num_splits + split);
+      const long prow_idx = (orow * hq + h) * sp.num_splits + split;
       if (l_run > 0.f) {
         float inv_l = 1.f / l_run;
         if constexpr (FP8) inv_l *= v_scale[kh];   // once per normalised row
@@ -487,7 +536,7 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
   } else if (in_range) {
     float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
     if constexpr (FP8) inv_l *= v_scale[kh];   // once per normalised row
-    short* op = O + ((long)(b * (long)sq + jr) * hq + h) * D;
+    short* op = O + (orow * hq + h) * D;
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
 #pragma unroll
@@ -501,11 +550,30 @@ void fa_kvcache_mq_kernel(const short* __restrict__ Q,
       }
     }
     if (hi == 0) {
-      LSE[((long)b * hq + h) * sq + jr] =
-          (l_run > 0.f) ? m_run + __logf(l_run) : -INFINITY;
+      LSE[lse_idx] = (l_run > 0.f) ? m_run + __logf(l_run) : -INFINITY;
     }
   }
 }
+
+// In HIP the second launch-bounds argument is waves per SIMD: 2 gives a
+// 256-VGPR budget (the 64 KB of LDS at d = 128 admit 2 workgroups per CU).
+template <int D, bool FP16, bool PAGED, bool FP8, bool SPLIT>
+__global__ __launch_bounds__(MQ_THREADS, 2)
+void fa_kvcache_mq_kernel(MQ_PARAMS, MqSplit<SPLIT> sp) {
+  mq_body<D, FP16, PAGED, FP8, SPLIT, false>(MQ_PASS, sp, MqPacked<false>{});
+}
+
+// The ladder behind the packed prologue, built exactly as the padded kernel:
+// its tiles are bitwise that kernel's.
+template <int D, bool FP16, bool PAGED, bool FP8, bool SPLIT>
+__global__ __launch_bounds__(MQ_THREADS, 2)
+void fa_kvcache_varlen_kernel(MQ_PARAMS, MqSplit<SPLIT> sp,
+                              MqPacked<true> pk) {
+  mq_body<D, FP16, PAGED, FP8, SPLIT, true>(MQ_PASS, sp, pk);
+}
+#undef MQ_PARAMS
+#undef MQ_PASS
+
 
 // ---------------------------------------------------------------------------
 // host side
@@ -524,12 +592,15 @@ void fa_kvcache_mq_combine_kernel(const float* __restrict__ o_part,
                                   const float* __restrict__ lse_part,
                                   short* __restrict__ O,
                                   float* __restrict__ LSE, long rows, int sq,
-                                  int hq, int num_splits) {
+                                  int hq, int num_splits,
+                                  const int* __restrict__ cu_end) {
   using ET = AttnElem<FP16>;
   constexpr int LPR = D / 4;                     // lanes per row
   constexpr int RPB = MQ_COMBINE_THREADS / LPR;  // rows per workgroup
   const long row = (long)blockIdx.x * RPB + threadIdx.x / LPR;
   if (row >= rows) return;
+  // packed layout (b = 1, sq = T): rows at or past cu_q[b] hold no partials
+  if (cu_end != nullptr && row / hq >= min(max(*cu_end, 0), sq)) return;
   const int d = (threadIdx.x % LPR) * 4;
   const float* lp = lse_part + row * num_splits;
   float mx = -INFINITY;
@@ -625,7 +696,7 @@ void mq_launch(const torch::Tensor& q, const torch::Tensor& k,
                      dim3((unsigned)((out_rows + RPB - 1) / RPB)),
                      dim3(MQ_COMBINE_THREADS), 0, stream, o_part, lse_part,
                      (short*)o.data_ptr(), lse.data_ptr<float>(), out_rows,
-                     sq, hq, ns);
+                     sq, hq, ns, nullptr);
 }
 
 constexpr const char* MQ_OP = "fa_kvcache_mq";
@@ -712,7 +783,167 @@ std::vector<torch::Tensor> mq_run(const torch::Tensor& q,
   return {o, lse};
 }
 
+// ---- packed (cu_seqlens) layout ---------------------------------------------
+
+constexpr const char* MQV_OP = "fa_kvcache_varlen";
+constexpr long MQV_MAX_SEQS = 1024;   // the work-item scan is linear in b
+
+// Row tiles of all sequences for one kv head, from the shapes alone: a
+// sequence's last tile may be partial, hence + b. Workgroups past the real
+// count exit after the scan.
+inline long mqv_items(long T, long rep, long b) {
+  return (T * rep) / MQ_ROWS + b;
+}
+
+template <int D, bool FP16, bool PAGED, bool FP8>
+void mqv_launch(const torch::Tensor& q, const torch::Tensor& k,
+                const torch::Tensor& v, const int* klp, const int* cu_q,
+                int b, torch::Tensor& o, torch::Tensor& lse, int cap,
+                float scale, int wl, const int* bt, int page_shift,
+                const float* k_scale, const float* v_scale, int ns,
+                float* o_part, float* lse_part, hipStream_t stream) {
+  const int T = q.size(0), hq = q.size(1);
+  const int hk = k.size(2);
+  const int items = (int)mqv_items(T, hq / hk, b);
+  const int lds = 4 * MQ_KVB * D * 2;
+  const MqPacked<true> pk{cu_q, b};
+#define MQV_KERNEL_ARGS                                                      \
+  (const short*)q.data_ptr(), (const void*)k.data_ptr(),                     \
+      (const void*)v.data_ptr(), klp, nullptr, (short*)o.data_ptr(),         \
+      lse.data_ptr<float>(), T, cap, hq, hk, (long)k.stride(0),              \
+      (long)k.stride(1), (long)v.stride(0), (long)v.stride(1), scale, wl,    \
+      bt, page_shift, PAGED ? (int)k.size(0) : 0, k_scale, v_scale
+  if (ns == 1) {
+    hipLaunchKernelGGL((fa_kvcache_varlen_kernel<D, FP16, PAGED, FP8, false>),
+                       dim3(items, hk, 1), dim3(MQ_THREADS), lds, stream,
+                       MQV_KERNEL_ARGS, MqSplit<false>{}, pk);
+    return;
+  }
+  hipLaunchKernelGGL((fa_kvcache_varlen_kernel<D, FP16, PAGED, FP8, true>),
+                     dim3(items * ns, hk, 1), dim3(MQ_THREADS), lds, stream,
+                     MQV_KERNEL_ARGS, MqSplit<true>{o_part, lse_part, ns},
+                     pk);
+#undef MQV_KERNEL_ARGS
+  // the padded combine with b = 1, sq = T: partials by row t * hq + h,
+  // lse [hq, T]
+  constexpr int RPB = MQ_COMBINE_THREADS / (D / 4);
+  const long out_rows = (long)T * hq;
+  hipLaunchKernelGGL((fa_kvcache_mq_combine_kernel<D, FP16>),
+                     dim3((unsigned)((out_rows + RPB - 1) / RPB)),
+                     dim3(MQ_COMBINE_THREADS), 0, stream, o_part, lse_part,
+                     (short*)o.data_ptr(), lse.data_ptr<float>(), out_rows, T,
+                     hq, ns, cu_q + b);
+}
+
+// Shape-only checks, no host sync.
+template <bool PAGED, bool FP8>
+std::vector<torch::Tensor> mqv_run(const torch::Tensor& q,
+                                   const torch::Tensor& k_cache,
+                                   const torch::Tensor& v_cache,
+                                   const torch::Tensor& k_lens,
+                                   const torch::Tensor& cu_q,
+                                   const torch::Tensor& block_table,
+                                   const torch::Tensor& k_scale,
+                                   const torch::Tensor& v_scale,
+                                   double softmax_scale, long wl,
+                                   long num_splits) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 3 && q.is_contiguous(),
+              "fa_kvcache_varlen: q must be a contiguous GPU [T, hq, d]");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 ||
+                  q.scalar_type() == torch::kHalf,
+              "fa_kvcache_varlen: bf16/fp16 only");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0);
+  TORCH_CHECK(cu_q.is_cuda() && cu_q.device() == q.device() &&
+                  cu_q.scalar_type() == torch::kInt32 && cu_q.dim() == 1 &&
+                  cu_q.size(0) >= 2 && cu_q.is_contiguous(),
+              "fa_kvcache_varlen: cu_q must be an int32 [b + 1] on q's GPU");
+  const long T = q.size(0), hq = q.size(1), D = q.size(2);
+  const long b = cu_q.size(0) - 1;
+  TORCH_CHECK(b <= MQV_MAX_SEQS, "fa_kvcache_varlen: at most ", MQV_MAX_SEQS,
+              " sequences per call, got ", b);
+  // q as [b, T, hq, d] (a stride-0 view) for the checks the padded op shares
+  const torch::Tensor qb = q.unsqueeze(0).expand({b, T, hq, D});
+  kvc_check_cache(MQV_OP, k_cache, qb, "k_cache", FP8);
+  kvc_check_cache(MQV_OP, v_cache, qb, "v_cache", FP8);
+  TORCH_CHECK(k_cache.sizes() == v_cache.sizes(),
+              "fa_kvcache_varlen: k_cache and v_cache shapes differ");
+  const long hk = k_cache.size(2);
+  TORCH_CHECK(D == 64 || D == 128,
+              "fa_kvcache_varlen: head_dim must be 64 or 128");
+  TORCH_CHECK(hk > 0 && hq % hk == 0, "fa_kvcache_varlen: needs h_k | h_q");
+  const long rep = hq / hk;
+  TORCH_CHECK(hk <= 65535 && T * rep <= (1L << 30),
+              "fa_kvcache_varlen: heads / rows out of range");
+  const int* klp = kvc_check_lens(MQV_OP, k_lens, qb, "k_lens");
+  const KvcGeometry geo = kvc_check_geometry(MQV_OP, qb, k_cache, block_table);
+  const float *ks = nullptr, *vs = nullptr;
+  if constexpr (FP8) {
+    ks = kvc_check_scale(MQV_OP, k_scale, k_cache, "k_scale");
+    vs = kvc_check_scale(MQV_OP, v_scale, v_cache, "v_scale");
+  }
+  wl = std::min<long>(wl, 1L << 30);
+
+  TORCH_CHECK(num_splits >= 0 && num_splits <= MQ_SPLIT_LIMIT,
+              "fa_kvcache_varlen: num_splits must be in [0, ", MQ_SPLIT_LIMIT,
+              "] (0: chosen from the shapes, 1: no split), got ", num_splits);
+  const long items = mqv_items(T, rep, b);
+  long ns = num_splits;
+  if (ns == 0)
+    // the work items take the place of b * row_tiles: T * rep rows alone
+    // would count 8 decoding rows as one tile and split 8 times too often
+    ns = mq_choose_num_splits(
+        1, hk, items * MQ_ROWS, geo.cap,
+        at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  if (ns > 1)
+    TORCH_CHECK(items * ns <= (1L << 23) && T * hq <= (1L << 26),
+                "fa_kvcache_varlen: too many rows for num_splits = ", ns,
+                "; use num_splits = 1");
+
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({hq, T}, q.options().dtype(torch::kFloat32));
+  if (T == 0) return {o, lse};
+  torch::Tensor o_part, lse_part;  // no memset: see the kernels
+  float *opp = nullptr, *lpp = nullptr;
+  if (ns > 1) {
+    o_part = torch::empty({T, hq, ns, D}, lse.options());
+    lse_part = torch::empty({T, hq, ns}, lse.options());
+    opp = o_part.data_ptr<float>();
+    lpp = lse_part.data_ptr<float>();
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+#define MQV_LAUNCH(DD)                                                       \
+  FP16_SWITCH(q.scalar_type() == torch::kHalf,                               \
+              mqv_launch<DD, kFP16, PAGED, FP8>(                             \
+                  q, k_cache, v_cache, klp, cu_q.data_ptr<int>(), (int)b, o, \
+                  lse, (int)geo.cap, (float)softmax_scale, (int)wl,          \
+                  geo.table, geo.page_shift, ks, vs, (int)ns, opp, lpp,      \
+                  stream))
+  if (D == 128) MQV_LAUNCH(128); else MQV_LAUNCH(64);
+#undef MQV_LAUNCH
+  HIP_CHECK_LAST();
+  return {o, lse};
+}
+
 }  // namespace
+
+// The packed (cu_seqlens) query layout of fa_kvcache_mq: q [T, hq, d], cu_q
+// int32 [b + 1]; sequence i owns rows [cu_q[i], cu_q[i+1]), its last tokens.
+// Returns o [T, hq, d] and lse [hq, T]; rows at or past cu_q[b] are left
+// unwritten. The other arguments are fa_kvcache_mq's.
+std::vector<torch::Tensor> fa_kvcache_varlen(
+    torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+    torch::Tensor k_lens, torch::Tensor cu_q, torch::Tensor block_table,
+    torch::Tensor k_scale, torch::Tensor v_scale, double softmax_scale,
+    long wl, long num_splits) {
+  const bool fp8 = kvc_present(k_scale);
+  TORCH_CHECK(fp8 == kvc_present(v_scale),
+              "fa_kvcache_varlen: k_scale and v_scale come together");
+  auto run = kvc_present(block_table)
+                 ? (fp8 ? mqv_run<true, true> : mqv_run<true, false>)
+                 : (fp8 ? mqv_run<false, true> : mqv_run<false, false>);
+  return run(q, k_cache, v_cache, k_lens, cu_q, block_table, k_scale,
+             v_scale, softmax_scale, wl, num_splits);
+}
 
 // q_lens, block_table, k_scale and v_scale are optional: an undefined or
 // empty 1-d tensor means absent. With a table the caches are page pools

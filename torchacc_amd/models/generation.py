@@ -263,6 +263,23 @@ class PagedKVCache:
         pad = (positions < 0) | (positions >= cap)
         return torch.where(pad.reshape(-1), torch.full_like(slots, -1), slots)
 
+    def slot_indices_packed(self, positions: torch.Tensor,
+                            seq_ids: torch.Tensor) -> torch.Tensor:
+        """``slot_indices_ragged`` for a packed step: token t of the step
+        belongs to sequence seq_ids[t] and sits at positions[t] (both [T],
+        device, int32 or int64) -> flat slots [T] (int64), -1 where the
+        position is negative or past the table's capacity. Position and
+        sequence id are clamped before the table lookup. Pure device
+        arithmetic; captures into a graph."""
+        positions, seq_ids = positions.long(), seq_ids.long()
+        cap = self.table_width * self.page_size
+        pos = positions.clamp(0, cap - 1)
+        page = self.table[seq_ids.clamp(0, self.b - 1),
+                          pos >> self.shift].long()
+        slots = page * self.page_size + (pos & (self.page_size - 1))
+        pad = (positions < 0) | (positions >= cap)
+        return torch.where(pad, torch.full_like(slots, -1), slots)
+
     def begin_step(self, positions: torch.Tensor):
         """Compute the slots the step's tokens are written to, once for all
         layers."""

@@ -11,6 +11,13 @@ place: ``flash_attn_with_kvcache`` when every row holds exactly one token,
 ``flash_attn_chunk_with_kvcache`` with ``q_seqlens`` otherwise. Every piece of
 a prompt, the first included, attends the cache it has just written.
 
+``packed=True`` runs a mixed step on its real tokens only: the step's T tokens
+lie along one axis (ids [1, T], with ``cu_seqlens_q`` giving every row's
+share) and attend through ``flash_attn_varlen_with_kvcache``, so one long
+prefill piece no longer pads every decoding row to its length in the GEMMs,
+norms and the LM head. All-decode steps are unchanged. The default keeps the
+padded step.
+
 Admission is FIFO. A waiting request takes the lowest free row once the pool
 has pages for its prompt plus ``max_new_tokens``; they are reserved there and
 then, so a running request never waits for memory (no preemption, no swap, no
@@ -35,6 +42,7 @@ from typing import Optional
 import torch
 
 from ..ops.flash_attn import (flash_attn_chunk_with_kvcache,
+                              flash_attn_varlen_with_kvcache,
                               flash_attn_with_kvcache, rope_kv_cache_write)
 from ..ops.rmsnorm import fused_add_rms_norm
 from .generation import PagedKVCache, _configure_scales, _is_fp8
@@ -59,11 +67,12 @@ class ContinuousBatcher:
     """See the module docstring. ``max_len`` bounds prompt + new tokens of one
     request (the block table's width); ``num_pages`` pages of ``page_size``
     tokens are shared by all rows. ``kv_dtype="fp8"`` needs ``kv_scales``
-    (one ``(k_scale, v_scale)`` per layer, as in ``generate``)."""
+    (one ``(k_scale, v_scale)`` per layer, as in ``generate``). ``packed``:
+    see the module docstring."""
 
     def __init__(self, model, max_batch: int, num_pages: int, page_size: int,
                  max_len: int, prefill_chunk: int = 64, kv_dtype=None,
-                 kv_scales=None):
+                 kv_scales=None, packed: bool = False):
         assert max_batch >= 1 and prefill_chunk >= 1 and max_len >= 1
         fp8 = _is_fp8(kv_dtype)
         if fp8 and kv_scales is None:
@@ -77,6 +86,7 @@ class ContinuousBatcher:
         self.model = model
         self.max_batch = max_batch
         self.prefill_chunk = prefill_chunk
+        self.packed = packed
         self.pool = PagedKVCache.for_model(model, max_batch, num_pages,
                                            page_size, max_len,
                                            kv_dtype=kv_dtype)
@@ -159,34 +169,11 @@ class ContinuousBatcher:
             empty = torch.empty(0, self.model.config.vocab_size)
             return ([], empty) if return_logits else []
         active = [i for i in range(b) if n[i] > 0]
-        # host side of the step: ids | positions | lens | n | last-row index
-        tok = b * sq
-        pack = torch.zeros(2 * tok + 2 * b + len(active), dtype=torch.int64)
-        ids_h = pack[:tok].view(b, sq)
-        pos_h = pack[tok:2 * tok].view(b, sq)
-        pos_h.fill_(-1)
-        lens_h = pack[2 * tok:2 * tok + b]
-        n_h = pack[2 * tok + b:2 * tok + 2 * b]
-        last_h = pack[2 * tok + 2 * b:]
-        for r, i in enumerate(active):
-            req, c = self.rows[i], self.rows[i].cached
-            ids_h[i, :n[i]] = torch.tensor(req.seq[c:c + n[i]])
-            pos_h[i, :n[i]] = torch.arange(c, c + n[i])
-            lens_h[i] = c + n[i]
-            n_h[i] = n[i]
-            last_h[r] = i * sq + n[i] - 1
-        dev = pack.to(self.device)
-        ids = dev[:tok].view(b, sq)
-        positions = dev[tok:2 * tok]
-        self.pool.lens.copy_(dev[2 * tok:2 * tok + b])
-        q_lens = dev[2 * tok + b:2 * tok + 2 * b]
-        last = dev[2 * tok + 2 * b:]
-        slots = self.pool.slot_indices_ragged(positions.view(b, sq))
         decode = sq == 1 and len(active) == b
-        longest = int(lens_h.max())
-
-        logits = self._forward(ids, positions, slots, q_lens, last, decode,
-                               longest)
+        if self.packed and not decode:
+            logits = self._packed_step(n, active)
+        else:
+            logits = self._padded_step(n, active, sq, decode)
         tokens = logits.argmax(-1).tolist()     # the step's one D2H copy
 
         events, keep = [], []
@@ -210,9 +197,70 @@ class ContinuousBatcher:
             return events, logits[keep].float()
         return events
 
-    def _forward(self, ids, positions, slots, q_lens, last, decode, longest):
-        """ids [b, sq] -> logits [rows, vocab] of the active rows' last real
-        tokens."""
+    def _packed_step(self, n, active):
+        """The step on its T = sum(n) real tokens: logits [len(active),
+        vocab]."""
+        b, T = self.max_batch, sum(n)
+        # host side: ids | positions | sequence ids | lens | cu | last rows
+        pack = torch.zeros(3 * T + 2 * b + 1 + len(active), dtype=torch.int64)
+        ids_h, pos_h, seq_h = pack[:T], pack[T:2 * T], pack[2 * T:3 * T]
+        lens_h = pack[3 * T:3 * T + b]
+        cu_h = pack[3 * T + b:3 * T + 2 * b + 1]
+        last_h = pack[3 * T + 2 * b + 1:]
+        t, r = 0, 0
+        for i in range(b):
+            if n[i] > 0:
+                req, c = self.rows[i], self.rows[i].cached
+                ids_h[t:t + n[i]] = torch.tensor(req.seq[c:c + n[i]])
+                pos_h[t:t + n[i]] = torch.arange(c, c + n[i])
+                seq_h[t:t + n[i]] = i
+                lens_h[i] = c + n[i]
+                last_h[r] = t + n[i] - 1
+                t, r = t + n[i], r + 1
+            cu_h[i + 1] = t
+        dev = pack.to(self.device)
+        positions = dev[T:2 * T]
+        self.pool.lens.copy_(dev[3 * T:3 * T + b])
+        slots = self.pool.slot_indices_packed(positions, dev[2 * T:3 * T])
+        return self._forward(dev[:T].view(1, T), positions, slots, None,
+                             dev[3 * T + 2 * b + 1:], False,
+                             int(lens_h.max()),
+                             cu=dev[3 * T + b:3 * T + 2 * b + 1])
+
+    def _padded_step(self, n, active, sq, decode):
+        """The step as [b, sq] with padding: logits [len(active), vocab]."""
+        b = self.max_batch
+        # host side of the step: ids | positions | lens | n | last-row index
+        tok = b * sq
+        pack = torch.zeros(2 * tok + 2 * b + len(active), dtype=torch.int64)
+        ids_h = pack[:tok].view(b, sq)
+        pos_h = pack[tok:2 * tok].view(b, sq)
+        pos_h.fill_(-1)
+        lens_h = pack[2 * tok:2 * tok + b]
+        n_h = pack[2 * tok + b:2 * tok + 2 * b]
+        last_h = pack[2 * tok + 2 * b:]
+        for r, i in enumerate(active):
+            req, c = self.rows[i], self.rows[i].cached
+            ids_h[i, :n[i]] = torch.tensor(req.seq[c:c + n[i]])
+            pos_h[i, :n[i]] = torch.arange(c, c + n[i])
+            lens_h[i] = c + n[i]
+            n_h[i] = n[i]
+            last_h[r] = i * sq + n[i] - 1
+        dev = pack.to(self.device)
+        ids = dev[:tok].view(b, sq)
+        positions = dev[tok:2 * tok]
+        self.pool.lens.copy_(dev[2 * tok:2 * tok + b])
+        q_lens = dev[2 * tok + b:2 * tok + 2 * b]
+        last = dev[2 * tok + 2 * b:]
+        slots = self.pool.slot_indices_ragged(positions.view(b, sq))
+        longest = int(lens_h.max())
+        return self._forward(ids, positions, slots, q_lens, last, decode,
+                             longest)
+
+    def _forward(self, ids, positions, slots, q_lens, last, decode, longest,
+                 cu=None):
+        """ids [b, sq] (packed: [1, T], with cu) -> logits [rows, vocab] of
+        the active rows' last real tokens."""
         m, pool = self.model, self.pool
         b, sq = ids.shape
         delta = m.embed_tokens(ids)
@@ -233,7 +281,12 @@ class ContinuousBatcher:
             sw = getattr(getattr(attn, "cfg", None), "sliding_window", None)
             if sw is not None and longest > sw:
                 wl = sw
-            if decode:
+            if cu is not None:
+                o = flash_attn_varlen_with_kvcache(
+                    q[0], cache.k, cache.v, pool.lens, cu,
+                    window_size=(wl, -1), block_table=pool.table,
+                    **cache.scales())
+            elif decode:
                 o = flash_attn_with_kvcache(
                     q, cache.k, cache.v, cache_seqlens=pool.lens,
                     window_size=(wl, -1), block_table=pool.table,

@@ -1250,3 +1250,140 @@ def flash_attn_chunk_with_kvcache(q, k_cache, v_cache, cache_seqlens,
     if return_lse:
         return out, lse
     return out
+
+
+# ---------------------------------------------------------------------------
+# the same with a packed (cu_seqlens) query layout
+# ---------------------------------------------------------------------------
+
+def _ref_varlen_kvcache(q, k_cache, v_cache, lens, cu, softmax_scale, wl):
+    """fp32 composite for flash_attn_varlen_with_kvcache on a contiguous
+    cache: scatter the packed rows to the padded layout [b, T, hq, d] (row
+    cu[i] + j -> [i, j]), run ``_ref_chunk`` with q_seqlens = n, gather back.
+    cu is clamped as the kernel clamps it. Pure device arithmetic, no host
+    sync (hence sq = T). Rows at or past cu[b] come back as zero rows with
+    lse = -inf. Returns (out [T, hq, d], lse [hq, T])."""
+    T, hq, d = q.shape
+    b = cu.shape[0] - 1
+    dev = q.device
+    cu = cu.long().clamp(0, T)
+    start = cu[:-1]
+    n = (cu[1:] - start).clamp(min=0)
+    t = torch.arange(T, device=dev)
+    # owner of row t: the sequence whose [start, start + n) holds it
+    own = (t.view(1, T) >= start.view(b, 1)) & \
+          (t.view(1, T) < (start + n).view(b, 1))              # [b, T]
+    seq = own.float().argmax(dim=0)                            # [T]
+    live = own.any(dim=0)
+    j = (t - start[seq]).clamp(0, max(T - 1, 0))
+    padded = torch.zeros(b, max(T, 1), hq, d, dtype=q.dtype, device=dev)
+    zero = torch.zeros((), dtype=q.dtype, device=dev)
+    if T > 0:
+        # dead rows land on [seq, j] slots past n of their sequence or are
+        # masked to zero; either way q_seqlens hides them
+        padded.index_put_((seq, j), torch.where(live.view(T, 1, 1), q, zero),
+                          accumulate=True)
+    out, lse = _ref_chunk(padded, k_cache, v_cache, lens, n, softmax_scale,
+                          wl)
+    if T == 0:
+        return out[0, :0], lse[0, :, :0]
+    o = torch.where(live.view(T, 1, 1), out[seq, j],
+                    torch.zeros((), dtype=out.dtype, device=dev))
+    ninf = torch.full((), float("-inf"), device=dev)
+    l = torch.where(live.view(1, T), lse[seq, :, j].transpose(0, 1), ninf)
+    return o, l
+
+
+_warned_varlen_kv = set()
+
+
+def flash_attn_varlen_with_kvcache(q, k_cache, v_cache, cache_seqlens,
+                                   cu_seqlens_q, softmax_scale=None,
+                                   window_size=(-1, -1), return_lse=False,
+                                   block_table=None, k_scale=None,
+                                   v_scale=None, num_splits=0):
+    """``flash_attn_chunk_with_kvcache`` with the new tokens of all sequences
+    packed along one axis, inference only: a serving step with one prefill
+    piece and several decoding rows runs on the real rows only.
+
+    q [T, hq, d]; ``cu_seqlens_q`` (int32/int64 [b + 1], same device) gives
+    the rows of sequence i as [cu[i], cu[i+1]); they are its LAST n_i =
+    cu[i+1] - cu[i] tokens, already written into the cache, and n_i = 0 is
+    legal anywhere. The caches, ``cache_seqlens`` [b], ``block_table``,
+    ``k_scale`` / ``v_scale``, ``window_size`` and ``num_splits`` are those of
+    the chunk op, with b = the number of sequences: token cu[i] + j sits at
+    p = L_i - n_i + j and sees the keys [lo, p]; a row with p < 0 is a zero
+    row with lse = -inf. Both tensors are read on the device: no host sync,
+    and a captured graph follows new values of the same shapes.
+
+    Rows of q at or past cu[b] belong to no sequence; their rows of the
+    result are left unwritten (the torch path returns zeros there). The
+    kernel clamps what it reads from ``cu_seqlens_q`` (offsets into [0, T],
+    n_i >= 0), so a malformed tensor gives wrong numbers, never an
+    out-of-range access. At most 1024 sequences per call.
+
+    bf16/fp16 q with d in {64, 128} on the GPU (paged: a page size that is a
+    power of two >= 16) runs the PACKED instances of
+    csrc/flash_attn_kvcache_mq.hip. A work item is (sequence, kv head,
+    128-packed-row tile of the sequence's own n_i * (hq / hk) rows, split),
+    found on the device by a scan of ``cu_seqlens_q``; every tile runs the
+    chunk op's body, so a sequence's rows are bitwise that op's on the same
+    sequence at the same ``num_splits``. ``num_splits`` = 0 chooses from the
+    shapes (the floor(T * (hq / hk) / 128) + b work items per kv head), 1 is
+    unsplit, 2..128 forces that count for every sequence. Other GPU inputs, and the
+    CPU, run an fp32 composite (scatter to the padded layout, the chunk op's
+    composite, gather), also without a host sync. Returns out [T, hq, d],
+    and lse [hq, T] (fp32, natural log) with ``return_lse``."""
+    assert q.dim() == 3 and k_cache.dim() == 4 and v_cache.dim() == 4, \
+        "expected q [T, hq, d] and caches [b, cap, hk, d]"
+    assert (isinstance(num_splits, int) and not isinstance(num_splits, bool)
+            and num_splits >= 0), \
+        f"num_splits must be a non-negative int, got {num_splits!r}"
+    assert isinstance(cache_seqlens, torch.Tensor), \
+        "flash_attn_varlen_with_kvcache requires cache_seqlens"
+    cu = cu_seqlens_q
+    assert isinstance(cu, torch.Tensor) and cu.dim() == 1 \
+        and cu.shape[0] >= 2 and cu.dtype in (torch.int32, torch.int64) \
+        and cu.device == q.device, \
+        "cu_seqlens_q must be int32 or int64 [b + 1] on the device of q"
+    b = cu.shape[0] - 1
+    assert b <= 1024, f"at most 1024 sequences per call, got {b}"
+    if cu.dtype != torch.int32:
+        cu = cu.to(torch.int32)
+    # q as [b, T, hq, d] (a view) for the checks the three ops share
+    fp8, covered, lens, _, block_table, softmax_scale, wl = _kvcache_args(
+        "flash_attn_varlen_with_kvcache", q.unsqueeze(0).expand(b, -1, -1, -1),
+        k_cache, v_cache, cache_seqlens, None, softmax_scale, window_size,
+        block_table, k_scale, v_scale)
+    paged = block_table is not None
+
+    ext = dispatch(q)
+    if ext is not None and covered:
+        out, lse = ext.fa_kvcache_varlen(
+            q.contiguous(), k_cache, v_cache, lens.contiguous(),
+            cu.contiguous(), block_table.contiguous() if paged else _ABSENT,
+            k_scale if fp8 else _ABSENT, v_scale if fp8 else _ABSENT,
+            softmax_scale, wl, num_splits)
+    else:
+        if ext is not None:
+            key = (q.dtype, q.shape[-1],
+                   k_cache.shape[1] if paged else None, fp8)
+            if key not in _warned_varlen_kv:
+                _warned_varlen_kv.add(key)
+                from ..utils.logger import logger
+                logger.warning(
+                    "flash_attn_varlen_with_kvcache: dtype %s / head_dim %d /"
+                    " page_size %s / fp8 %s is not covered by the HIP kernel;"
+                    " running the fp32 composite on a copy of the cache on "
+                    "the device", *key)
+        if paged:
+            k_cache = _gather_pages(k_cache, block_table)
+            v_cache = _gather_pages(v_cache, block_table)
+        if fp8:
+            k_cache = dequantize_kv_fp8(k_cache, k_scale)
+            v_cache = dequantize_kv_fp8(v_cache, v_scale)
+        out, lse = _ref_varlen_kvcache(q, k_cache, v_cache, lens, cu,
+                                       softmax_scale, wl)
+    if return_lse:
+        return out, lse
+    return out
