@@ -32,6 +32,11 @@ def main():
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="run the prompt in pieces of at most this many "
                         "tokens (eager path)")
+    p.add_argument("--weight-dtype", default=None, choices=["fp8"],
+                   help="quantise the decoder projections to e4m3 weights "
+                        "(quantize_model_fp8; default: 16-bit weights)")
+    p.add_argument("--fp8-lm-head", action="store_true",
+                   help="with --weight-dtype fp8: quantise lm_head too")
     args = p.parse_args()
     gen_kw = {"kv_dtype": args.kv_dtype}
     if args.page_size is not None:
@@ -53,6 +58,9 @@ def main():
             model = LlamaForCausalLM(mcfg).to(torch.bfloat16).eval()
     else:
         model = LlamaForCausalLM(mcfg).eval()
+    if args.weight_dtype == "fp8":
+        from torchacc_amd.ops import quantize_model_fp8
+        quantize_model_fp8(model, include_lm_head=args.fp8_lm_head)
     ids = torch.randint(0, mcfg.vocab_size, (args.batch, args.prompt),
                         device=dev)
 
@@ -75,6 +83,10 @@ def main():
         torch.cuda.synchronize()
     t1 = time.perf_counter()
     new_tokens = (out.shape[1] - args.prompt) * args.batch
+    extra = {}
+    if args.weight_dtype is not None:
+        extra = {"weight_dtype": args.weight_dtype,
+                 "fp8_lm_head": args.fp8_lm_head}
     print(json.dumps({
         "metric": "decode tokens/sec",
         "value": new_tokens / (t1 - t0),
@@ -85,7 +97,7 @@ def main():
         "graph": args.graph,
         "kv_dtype": args.kv_dtype or ("bf16" if on_gpu else "fp32"),
         "page_size": args.page_size, "prefill_chunk": args.prefill_chunk,
-        "seconds": t1 - t0,
+        "seconds": t1 - t0, **extra,
     }))
 
 

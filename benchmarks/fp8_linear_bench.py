@@ -1,0 +1,121 @@
+"""fp8-weight linear (ops.fp8_linear, csrc/fp8_linear.hip) against the 16-bit
+path (ops.linear.tuned_linear) on the Llama-2-7B / Llama-3-8B projection and
+LM-head shapes, decode-sized batches.
+
+  python benchmarks/fp8_linear_bench.py [--shapes 4096x4096,...] [--m 1,16]
+      [--splits 0,1,4] [--out table.md]
+
+Per (N, K, M) the two paths run alternating in one process, 16-bit first and
+last, so the difference of the two 16-bit windows shows the run-to-run
+spread. Each path cycles through enough weight copies (>= 512 MiB) that no
+call finds its weights in a cache. Times are device-event windows after a
+warm-up. "hbm%" is weight bytes / time over the 8 TB/s HBM peak. --splits
+lists K-split counts to force on the kernel (0 = its own choice). The fp8
+column is the kernel itself at every M, also above FP8_LINEAR_MAX_M where
+ops.fp8_linear would not route to it: that is how the crossover is found.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+
+import torch  # noqa: E402
+
+HBM_PEAK = 8.0e12   # bytes/s, MI355X
+SHAPES = [(4096, 4096), (11008, 4096), (4096, 11008), (32000, 4096),
+          (1024, 4096), (14336, 4096), (4096, 14336), (128256, 4096)]
+MS = [1, 2, 4, 8, 16, 32, 64, 128]
+
+
+def _window(fn, copies, iters):
+    start, end = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    start.record()
+    for i in range(iters):
+        fn(i % copies)
+    end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / iters * 1e3   # us per call
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--shapes", default=None, help="NxK,NxK,...")
+    p.add_argument("--m", default=None, help="batch sizes, comma separated")
+    p.add_argument("--splits", default="0")
+    p.add_argument("--window-ms", type=float, default=40.0)
+    p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--out", default=None, help="also write a markdown table")
+    args = p.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("fp8_linear_bench needs a GPU: nothing is measured without")
+    from torchacc_amd.ops import quantize_weight_fp8
+    from torchacc_amd.ops._backend import require_extension
+    from torchacc_amd.ops.linear import tuned_linear
+    ext = require_extension()
+    shapes = SHAPES if args.shapes is None else [
+        tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
+    ms = MS if args.m is None else [int(v) for v in args.m.split(",")]
+    splits = [int(v) for v in args.splits.split(",")]
+    rows = []
+    torch.manual_seed(0)
+    for n, k in shapes:
+        copies = max(2, -(-(512 << 20) // (n * k)))
+        w16 = [torch.randn(n, k, device="cuda", dtype=torch.bfloat16) * 0.02
+               for _ in range(copies)]
+        q = [quantize_weight_fp8(w) for w in w16]
+        for m in ms:
+            x = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
+            fns = {"w16": lambda i: tuned_linear(x, w16[i])}
+            for s in splits:
+                if s == 0:
+                    fns["fp8"] = lambda i: ext.fp8_linear(
+                        x, q[i][0], q[i][1], None, 0)
+                else:
+                    fns[f"fp8/s{s}"] = lambda i, s=s: ext.fp8_linear(
+                        x, q[i][0], q[i][1], None, s)
+            fns["w16b"] = fns["w16"]
+            with torch.no_grad():
+                est = {}
+                for name, fn in fns.items():       # warm-up, sizes the window
+                    _window(fn, copies, copies)
+                    est[name] = _window(fn, copies, 2 * copies)
+                t = {name: [] for name in fns}
+                for _ in range(args.reps):
+                    for name, fn in fns.items():
+                        iters = max(20, int(args.window_ms * 1e3 / est[name]))
+                        t[name].append(_window(fn, copies, iters))
+            us = {name: statistics.median(v) for name, v in t.items()}
+            row = {"n": n, "k": k, "m": m, "us": us,
+                   "spread": abs(us["w16"] - us["w16b"]) / us["w16"],
+                   "splits_auto": ext.fp8_linear_num_splits(
+                       n, k, torch.cuda.get_device_properties(0)
+                       .multi_processor_count)}
+            for name in us:
+                if name.startswith("fp8"):
+                    row[f"hbm_{name}"] = n * k / (us[name] * 1e-6) / HBM_PEAK
+                    row[f"ratio_{name}"] = us[name] / min(us["w16"],
+                                                          us["w16b"])
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del w16, q
+    if args.out:
+        names = [nm for nm in rows[0]["us"] if nm.startswith("fp8")]
+        with open(args.out, "w") as f:
+            f.write("| N | K | M | 16-bit us | 16-bit again us | spread | "
+                    + " | ".join(f"{nm} us | hbm% | vs 16-bit" for nm in names)
+                    + " |\n")
+            f.write("|" + "---|" * (6 + 3 * len(names)) + "\n")
+            for r in rows:
+                cells = [r["n"], r["k"], r["m"], f"{r['us']['w16']:.1f}",
+                         f"{r['us']['w16b']:.1f}", f"{r['spread']:.1%}"]
+                for nm in names:
+                    cells += [f"{r['us'][nm]:.1f}", f"{r['hbm_' + nm]:.0%}",
+                              f"{r['ratio_' + nm]:.2f}"]
+                f.write("| " + " | ".join(str(c) for c in cells) + " |\n")
+
+
+if __name__ == "__main__":
+    main()

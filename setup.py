@@ -29,6 +29,7 @@ sources = [
         "flash_attn_extra_fwd.hip",
         "flash_attn_extra_bwd.hip",
         "gemm.hip",
+        "fp8_linear.hip",
     )
 ]
 

@@ -118,6 +118,12 @@ torch::Tensor lt_gemm(torch::Tensor a, torch::Tensor b, bool ta, bool tb,
 std::string lt_gemm_algo_name(int64_t algo_index);
 torch::Tensor lt_gemv(torch::Tensor x, torch::Tensor w);
 
+// fp8_linear.hip; num_splits: 0 = chosen from (N, K) and the CU count
+torch::Tensor fp8_linear(torch::Tensor x, torch::Tensor w8,
+                         torch::Tensor scale,
+                         c10::optional<torch::Tensor> bias, long num_splits);
+long fp8_linear_num_splits(long n, long k, long num_cus);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torchacc_amd CDNA4 (gfx950) kernels";
   m.def("rmsnorm_forward", &rmsnorm_forward);
@@ -148,4 +154,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("out") = pybind11::none());
   m.def("lt_gemm_algo_name", &lt_gemm_algo_name);
   m.def("lt_gemv", &lt_gemv);
+  m.def("fp8_linear", &fp8_linear, pybind11::arg("x"), pybind11::arg("w8"),
+        pybind11::arg("scale"), pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("num_splits") = 0);
+  m.def("fp8_linear_num_splits", &fp8_linear_num_splits);
 }

@@ -1,0 +1,392 @@
+// Weight-only fp8 (e4m3) linear layer for decode-sized batches (W8A16):
+//   y[M,N] = (x[M,K] @ dequant(W8[N,K])^T) * scale[N] (+ bias[N])
+// x, y bf16 or fp16; W8 e4m3 codes, row-major; one fp32 scale per output
+// channel. A decode step is bound by reading the projection weights once;
+// e4m3 halves those bytes against the 16-bit paths in gemm.hip.
+//
+// Matrix instruction: v_mfma_f32_16x16x32_{bf16,f16} with the WEIGHTS as the
+// A operand (16 output channels per tile, lane l holds row l&15, k-slots
+// 8*(l>>4)..+7) and up to 16 activation rows as the B operand (lane l holds
+// column l&15). The result is y^T: lane l owns activation row l&15 and the
+// four consecutive channels 4*(l>>4)..+3, which is an 8-byte store along N.
+// A wave owns NT = 2 channel tiles and MT in {1,2,4} column blocks; one
+// converted A fragment feeds MT MFMAs and one B fragment feeds NT.
+//
+// Weight stream: a lane reads 16 contiguous codes of its row per 16-byte
+// load; the four lane groups of a row cover 64 contiguous bytes, and a step
+// issues the two loads of a 128-byte line back to back. The 16 codes feed two
+// MFMA K-steps (codes 0..7, then 8..15). The reduction order inside K is
+// free, so the x fragment simply follows the same permutation: lane (j, g)
+// reads x[j][k0 + 16g + 8s .. +7] for K-step s, 32 contiguous bytes.
+//
+// e4m3 -> 16 bit is exact (3 mantissa bits): v_cvt_pk_f32_fp8, then
+// v_cvt_pk_bf16_f32 (bf16) or v_cvt_pkrtz (fp16). The channel scale
+// multiplies the fp32 accumulator once, in the epilogue.
+//
+// Filling the device: a workgroup is 4 waves on the same 32 channels, each
+// wave on its own contiguous run of 128-code steps; the four accumulators are
+// summed through LDS in wave order. Where N/32 workgroups are too few, K is
+// also cut across S workgroups (grid.y) that write fp32 partials, summed in
+// split order by a second launch (the split-KV combine pattern). No atomics.
+// S and every K boundary come from (N, K) and the CU count alone, never from
+// M, and an output row depends on its own B column only: a row's bits do not
+// depend on the batch it sits in, nor on its position.
+//
+// Activations are read straight from global memory (they are L2-resident).
+// With K split across the waves of a workgroup no two waves read the same x
+// bytes, so an LDS stage could not cut the traffic and would put a barrier
+// per chunk on the weight stream (profiles/r15_fp8_linear.md). Rows >= M are
+// read from row M-1 and never stored, so the MFMA path has no predicate.
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+
+#include <algorithm>
+
+#include "common.h"
+#include "attn_common.h"
+
+// packed fp32 VALU forms are kept out of this file's device code
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
+                             apply_to = function)
+
+namespace {
+
+constexpr int FP8L_WAVES = 4;     // waves per workgroup, all on the same tiles
+constexpr int FP8L_NT = 2;        // 16-channel tiles per wave
+constexpr int FP8L_BN = 16 * FP8L_NT;
+constexpr int FP8L_STEP = 128;    // codes per wave step: one 128-byte line/row
+constexpr int FP8L_MAX_SPLITS = 16;
+// workgroups per CU the K split aims for; 2 x 4 waves with a whole step of
+// loads in flight each (profiles/r15_fp8_linear.md)
+constexpr int FP8L_WG_PER_CU = 2;
+
+typedef __bf16 fp8l_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 fp8l_bf16x2 __attribute__((ext_vector_type(2)));
+
+template <bool FP16>
+struct Fp8lElem;
+
+template <>
+struct Fp8lElem<false> {
+  // two e4m3 codes as fp32 -> bf16 pair in one dword. v_cvt_pk_bf16_f32 is
+  // exact here (3 mantissa bits). Integer forms on the bit-cast elements
+  // (shift/mask, __builtin_amdgcn_perm) were compiled to read element 0 of
+  // the convert's result pair twice, so the float-domain convert is used.
+  static DEVINLINE unsigned pack(f32x2 f) {
+    return __builtin_bit_cast(unsigned,
+                              __builtin_convertvector(f, fp8l_bf16x2));
+  }
+  static DEVINLINE f32x4 mfma(attn_u32x4 a, attn_u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+        __builtin_bit_cast(fp8l_bf16x8, a), __builtin_bit_cast(fp8l_bf16x8, b),
+        c, 0, 0, 0);
+  }
+};
+
+template <>
+struct Fp8lElem<true> {
+  static DEVINLINE unsigned pack(f32x2 f) {
+    return AttnElem<true>::cvt_pk(f[0], f[1]);
+  }
+  static DEVINLINE f32x4 mfma(attn_u32x4 a, attn_u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(
+        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
+        c, 0, 0, 0);
+  }
+};
+
+// 8 e4m3 codes (two dwords) -> one 16-bit x8 MFMA A fragment
+template <bool FP16>
+DEVINLINE attn_u32x4 fp8l_cvt8(unsigned c0, unsigned c1) {
+  attn_u32x4 a;
+  a[0] = Fp8lElem<FP16>::pack(__builtin_amdgcn_cvt_pk_f32_fp8((int)c0, false));
+  a[1] = Fp8lElem<FP16>::pack(__builtin_amdgcn_cvt_pk_f32_fp8((int)c0, true));
+  a[2] = Fp8lElem<FP16>::pack(__builtin_amdgcn_cvt_pk_f32_fp8((int)c1, false));
+  a[3] = Fp8lElem<FP16>::pack(__builtin_amdgcn_cvt_pk_f32_fp8((int)c1, true));
+  return a;
+}
+
+// Scale, bias, convert and store channels n..n+3 (n % 4 == 0) of row m.
+template <bool FP16>
+DEVINLINE void fp8l_finish4(f32x4 v, long m, int n, int N,
+                            const float* __restrict__ scale,
+                            const short* __restrict__ bias,
+                            short* __restrict__ y) {
+  if ((N & 3) == 0) {  // then n + 3 < N and the row start is 8-byte aligned
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + n);
+    float o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = v[r] * sc[r];
+    if (bias != nullptr) {
+      const s16x4 bv = *reinterpret_cast<const s16x4*>(bias + n);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] += AttnElem<FP16>::to_f32(bv[r]);
+    }
+    s16x4 ov;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ov[r] = AttnElem<FP16>::from_f32(o[r]);
+    *reinterpret_cast<s16x4*>(y + m * N + n) = ov;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (n + r < N) {
+        float o = v[r] * scale[n + r];
+        if (bias != nullptr) o += AttnElem<FP16>::to_f32(bias[n + r]);
+        y[m * N + n + r] = AttnElem<FP16>::from_f32(o);
+      }
+    }
+  }
+}
+
+// One 128-code step of a wave: for each half (64 codes) every lane loads its
+// 16 codes of both tiles and its 16 activations of every column block, then
+// 2 K-steps x NT x MT MFMAs. TAIL is the one ragged step at the end of K
+// (K % 128 != 0): 16-code granules at or past K contribute zeros.
+template <bool FP16, int MT, bool TAIL>
+DEVINLINE void fp8l_step(const unsigned char* const (&wrow)[FP8L_NT],
+                         const short* const (&xrow)[MT], int kl, int K,
+                         f32x4 (&acc)[FP8L_NT][MT]) {
+  attn_u32x4 wv[2][FP8L_NT];
+  attn_u32x4 xv[2][MT][2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = kl + h * 64;          // this lane's 16 codes: [k, k + 16)
+    const bool live = !TAIL || k < K;
+    const int kc = live ? k : 0;
+#pragma unroll
+    for (int nt = 0; nt < FP8L_NT; ++nt) {
+      wv[h][nt] = *reinterpret_cast<const attn_u32x4*>(wrow[nt] + kc);
+      if (TAIL && !live) wv[h][nt] = attn_u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        xv[h][mt][s] =
+            *reinterpret_cast<const attn_u32x4*>(xrow[mt] + kc + 8 * s);
+        if (TAIL && !live) xv[h][mt][s] = attn_u32x4{0u, 0u, 0u, 0u};
+      }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+      for (int nt = 0; nt < FP8L_NT; ++nt) {
+        const attn_u32x4 a =
+            fp8l_cvt8<FP16>(wv[h][nt][2 * s], wv[h][nt][2 * s + 1]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[nt][mt] = Fp8lElem<FP16>::mfma(a, xv[h][mt][s], acc[nt][mt]);
+      }
+    }
+  }
+}
+
+// grid = (ceil(N/32), S, ceil(M/64)); block = 256.
+// S == 1: writes y. S > 1: writes raw fp32 sums to part[S][M][N].
+template <bool FP16, int MT>
+__global__ __launch_bounds__(FP8L_WAVES * WAVE)
+void fp8_linear_kernel(const short* __restrict__ x,
+                       const unsigned char* __restrict__ w,
+                       const float* __restrict__ scale,
+                       const short* __restrict__ bias,
+                       short* __restrict__ y, float* __restrict__ part,
+                       int M, int N, int K) {
+  __shared__ f32x4 red[FP8L_WAVES][FP8L_NT * MT][WAVE];
+  const int tid = threadIdx.x;
+  const int wave = tid / WAVE, lane = tid % WAVE;
+  const int j = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * FP8L_BN;
+  const int split = blockIdx.y, S = gridDim.y;
+  const int mb = blockIdx.z * 64;
+
+  // contiguous, balanced runs of steps over the S * 4 wave slots
+  const int T = (K + FP8L_STEP - 1) / FP8L_STEP, Tfull = K / FP8L_STEP;
+  const int slots = S * FP8L_WAVES, slot = split * FP8L_WAVES + wave;
+  const int t0 = (int)((long)slot * T / slots);
+  const int t1 = (int)((long)(slot + 1) * T / slots);
+
+  // rows past the end are clamped: loaded, multiplied, never stored
+  const unsigned char* wrow[FP8L_NT];
+#pragma unroll
+  for (int nt = 0; nt < FP8L_NT; ++nt)
+    wrow[nt] = w + (long)min(n0 + nt * 16 + j, N - 1) * K;
+  const short* xrow[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+    xrow[mt] = x + (long)min(mb + mt * 16 + j, M - 1) * K;
+
+  f32x4 acc[FP8L_NT][MT];
+#pragma unroll
+  for (int nt = 0; nt < FP8L_NT; ++nt)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int tm = min(t1, Tfull);
+#pragma unroll 2
+  for (int t = t0; t < tm; ++t)
+    fp8l_step<FP16, MT, false>(wrow, xrow, t * FP8L_STEP + g * 16, K, acc);
+  if (t1 > Tfull)  // only the last slot, only when K % 128 != 0
+    fp8l_step<FP16, MT, true>(wrow, xrow, Tfull * FP8L_STEP + g * 16, K, acc);
+
+  // the four waves' sums, added in wave order
+#pragma unroll
+  for (int i = 0; i < FP8L_NT * MT; ++i) red[wave][i][lane] = acc[i / MT][i % MT];
+  __syncthreads();
+  for (int idx = tid; idx < FP8L_NT * MT * WAVE; idx += FP8L_WAVES * WAVE) {
+    const int i = idx / WAVE, l = idx % WAVE;
+    f32x4 v = red[0][i][l];
+#pragma unroll
+    for (int wv = 1; wv < FP8L_WAVES; ++wv) v += red[wv][i][l];
+    const int m = mb + (i % MT) * 16 + (l & 15);
+    const int n = n0 + (i / MT) * 16 + 4 * (l >> 4);
+    if (m >= M || n >= N) continue;
+    if (S == 1) {
+      fp8l_finish4<FP16>(v, m, n, N, scale, bias, y);
+    } else {
+      float* p = part + ((long)split * M + m) * N + n;
+      if ((N & 3) == 0) {
+        *reinterpret_cast<f32x4*>(p) = v;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < N) p[r] = v[r];
+      }
+    }
+  }
+}
+
+// y = (sum over splits, in split order) * scale + bias; a thread per four
+// channels of one row.
+template <bool FP16>
+__global__ __launch_bounds__(256)
+void fp8_linear_combine_kernel(const float* __restrict__ part,
+                               const float* __restrict__ scale,
+                               const short* __restrict__ bias,
+                               short* __restrict__ y, int M, int N, int S) {
+  const int n4 = (N + 3) / 4;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)M * n4) return;
+  const long m = idx / n4;
+  const int n = (int)(idx % n4) * 4;
+  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < S; ++s) {
+    const float* p = part + ((long)s * M + m) * N + n;
+    if ((N & 3) == 0) {
+      v += *reinterpret_cast<const f32x4*>(p);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (n + r < N) v[r] += p[r];
+    }
+  }
+  fp8l_finish4<FP16>(v, m, n, N, scale, bias, y);
+}
+
+}  // namespace
+
+#pragma clang attribute pop
+
+// Number of K splits across workgroups for an [N, K] weight on a device with
+// num_cus compute units. A function of (N, K, num_cus) only: the batch size
+// must not move a K boundary (batch invariance). Every wave slot keeps at
+// least one whole step.
+long fp8_linear_num_splits(long n, long k, long num_cus) {
+  const long wgs = (n + FP8L_BN - 1) / FP8L_BN;
+  const long steps = (k + FP8L_STEP - 1) / FP8L_STEP;
+  const long want = (FP8L_WG_PER_CU * num_cus + wgs - 1) / wgs;
+  const long cap = std::min<long>(FP8L_MAX_SPLITS, steps / FP8L_WAVES);
+  return std::max<long>(1, std::min(want, cap));
+}
+
+// y = (x @ dequant(w8)^T) * scale (+ bias). num_splits: 0 = chosen from
+// (N, K) and the CU count, otherwise forced (benchmarks, tests).
+torch::Tensor fp8_linear(torch::Tensor x, torch::Tensor w8,
+                         torch::Tensor scale,
+                         c10::optional<torch::Tensor> bias,
+                         long num_splits) {
+  TORCH_CHECK(x.is_cuda() && w8.is_cuda() && scale.is_cuda(),
+              "fp8_linear: GPU tensors required");
+  TORCH_CHECK(x.dim() == 2 && w8.dim() == 2 && scale.dim() == 1,
+              "fp8_linear: x [M,K], w8 [N,K], scale [N]");
+  const bool fp16 = x.scalar_type() == torch::kHalf;
+  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
+              "fp8_linear: x must be bf16 or fp16");
+  TORCH_CHECK(w8.scalar_type() == torch::kFloat8_e4m3fn,
+              "fp8_linear: w8 must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat,
+              "fp8_linear: scale must be fp32");
+  TORCH_CHECK(x.is_contiguous() && w8.is_contiguous() && scale.is_contiguous(),
+              "fp8_linear: contiguous operands");
+  TORCH_CHECK(w8.device() == x.device() && scale.device() == x.device(),
+              "fp8_linear: operands on different devices");
+  const long M = x.size(0), K = x.size(1), N = w8.size(0);
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 16 && K % 16 == 0,
+              "fp8_linear: K must be a positive multiple of 16");
+  TORCH_CHECK(w8.size(1) == K && scale.size(0) == N,
+              "fp8_linear: shape mismatch");
+  TORCH_CHECK(M * K < (1L << 31) && (M + 64) * N < (1L << 31),
+              "fp8_linear: problem too large");
+  const short* bias_p = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                    bias->scalar_type() == x.scalar_type() &&
+                    bias->dim() == 1 && bias->size(0) == N &&
+                    bias->is_contiguous(),
+                "fp8_linear: bias must be [N], contiguous, x's dtype/device");
+    bias_p = (const short*)bias->data_ptr();
+    TORCH_CHECK((uintptr_t)bias_p % 8 == 0, "fp8_linear: bias alignment");
+  }
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)w8.data_ptr() % 16 == 0 &&
+                  (uintptr_t)scale.data_ptr() % 16 == 0,
+              "fp8_linear: operands must be 16-byte aligned");
+
+  long S = num_splits;
+  if (S <= 0) {
+    S = fp8_linear_num_splits(
+        N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  }
+  const long steps = (K + FP8L_STEP - 1) / FP8L_STEP;
+  TORCH_CHECK(S <= FP8L_MAX_SPLITS, "fp8_linear: num_splits above ",
+              FP8L_MAX_SPLITS);
+  S = std::max<long>(1, std::min(S, steps));
+
+  auto y = torch::empty({M, N}, x.options());
+  torch::Tensor part;
+  float* part_p = nullptr;
+  if (S > 1) {
+    part = torch::empty({S, M, N}, x.options().dtype(torch::kFloat));
+    part_p = part.data_ptr<float>();
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  const dim3 grid((N + FP8L_BN - 1) / FP8L_BN, S, (M + 63) / 64);
+  const dim3 block(FP8L_WAVES * WAVE);
+  const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
+#define FP8L_LAUNCH(MTV)                                                      \
+  hipLaunchKernelGGL((fp8_linear_kernel<kFP16, MTV>), grid, block, 0, stream, \
+                     (const short*)x.data_ptr(),                              \
+                     (const unsigned char*)w8.data_ptr(),                     \
+                     scale.data_ptr<float>(), bias_p, (short*)y.data_ptr(),   \
+                     part_p, (int)M, (int)N, (int)K)
+  FP16_SWITCH(fp16, {
+    if (mt == 1) FP8L_LAUNCH(1);
+    else if (mt == 2) FP8L_LAUNCH(2);
+    else FP8L_LAUNCH(4);
+  });
+#undef FP8L_LAUNCH
+  HIP_CHECK_LAST();
+  if (S > 1) {
+    const long groups = M * ((N + 3) / 4);
+    FP16_SWITCH(fp16, {
+      hipLaunchKernelGGL((fp8_linear_combine_kernel<kFP16>),
+                         dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+                         stream, part_p, scale.data_ptr<float>(), bias_p,
+                         (short*)y.data_ptr(), (int)M, (int)N, (int)S);
+    });
+    HIP_CHECK_LAST();
+  }
+  return y;
+}

@@ -43,10 +43,12 @@ class _Tracer(fx.Tracer):
 
     def is_leaf_module(self, m, qualname):
         from ..ops.linear import TunedLinear
+        from ..ops.linear_fp8 import Fp8Linear
         from ..ops.rmsnorm import RMSNorm
-        if isinstance(m, (RMSNorm, TunedLinear)):
-            # TunedLinear.forward branches on device/dtype (GPU hipBLASLt
-            # vs F.linear) — leaf it like nn.Linear so fx never sees that
+        if isinstance(m, (RMSNorm, TunedLinear, Fp8Linear)):
+            # TunedLinear / Fp8Linear.forward branch on device/dtype (GPU
+            # kernels vs F.linear) — leaf them like nn.Linear so fx never
+            # sees that
             return True
         return super().is_leaf_module(m, qualname)
 
