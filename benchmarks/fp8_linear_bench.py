@@ -1,6 +1,7 @@
 """fp8-weight linear (ops.fp8_linear, csrc/fp8_linear.hip) against the 16-bit
 path (ops.linear.tuned_linear) on the Llama-2-7B / Llama-3-8B projection and
-LM-head shapes, decode-sized batches.
+LM-head shapes, decode-sized batches (the skinny kernel) and prefill-sized
+ones (the tiled fp8_gemm kernel).
 
   python benchmarks/fp8_linear_bench.py [--shapes 4096x4096,...] [--m 1,16]
       [--splits 0,1,4] [--out table.md]
@@ -13,6 +14,12 @@ warm-up. "hbm%" is weight bytes / time over the 8 TB/s HBM peak. --splits
 lists K-split counts to force on the kernel (0 = its own choice). The fp8
 column is the kernel itself at every M, also above FP8_LINEAR_MAX_M where
 ops.fp8_linear would not route to it: that is how the crossover is found.
+
+Above M = 64 two more columns run in the same alternation: "deq", the path
+ops.fp8_linear took there before fp8_gemm existed, written out here
+(dequantise the weight in memory, then tuned_linear), and "gemm", the tiled
+kernel ext.fp8_gemm (--splits also forces its K split, "gemm/sN"). For the
+gemm columns "mfma%" is 2*M*N*K / time over MFMA_PEAK.
 """
 import argparse
 import json
@@ -25,9 +32,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import torch  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes/s, MI355X
+# dense bf16/fp16 matrix peak of the MI355X, FLOP/s: AMD's product
+# specification (2.5 PFLOP/s without sparsity)
+MFMA_PEAK = 2.5e15
 SHAPES = [(4096, 4096), (11008, 4096), (4096, 11008), (32000, 4096),
           (1024, 4096), (14336, 4096), (4096, 14336), (128256, 4096)]
-MS = [1, 2, 4, 8, 16, 32, 64, 128]
+MS = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096]
+SKINNY_MAX_M = 128   # the skinny kernel is timed up to here
 
 
 def _window(fn, copies, iters):
@@ -69,12 +80,16 @@ def main():
         for m in ms:
             x = torch.randn(m, k, device="cuda", dtype=torch.bfloat16)
             fns = {"w16": lambda i: tuned_linear(x, w16[i])}
-            for s in splits:
-                if s == 0:
-                    fns["fp8"] = lambda i: ext.fp8_linear(
-                        x, q[i][0], q[i][1], None, 0)
-                else:
-                    fns[f"fp8/s{s}"] = lambda i, s=s: ext.fp8_linear(
+            for s in splits if m <= SKINNY_MAX_M else []:
+                name = "fp8" if s == 0 else f"fp8/s{s}"
+                fns[name] = lambda i, s=s: ext.fp8_linear(
+                    x, q[i][0], q[i][1], None, s)
+            if m > 64:
+                fns["deq"] = lambda i: tuned_linear(
+                    x, (q[i][0].float() * q[i][1][:, None]).to(x.dtype), None)
+                for s in splits:
+                    name = "gemm" if s == 0 else f"gemm/s{s}"
+                    fns[name] = lambda i, s=s: ext.fp8_gemm(
                         x, q[i][0], q[i][1], None, s)
             fns["w16b"] = fns["w16"]
             with torch.no_grad():
@@ -88,33 +103,57 @@ def main():
                         iters = max(20, int(args.window_ms * 1e3 / est[name]))
                         t[name].append(_window(fn, copies, iters))
             us = {name: statistics.median(v) for name, v in t.items()}
+            cus = torch.cuda.get_device_properties(0).multi_processor_count
             row = {"n": n, "k": k, "m": m, "us": us,
                    "spread": abs(us["w16"] - us["w16b"]) / us["w16"],
-                   "splits_auto": ext.fp8_linear_num_splits(
-                       n, k, torch.cuda.get_device_properties(0)
-                       .multi_processor_count)}
+                   "splits_auto": ext.fp8_linear_num_splits(n, k, cus),
+                   "gemm_splits_auto": ext.fp8_gemm_num_splits(m, n, k, cus)}
             for name in us:
                 if name.startswith("fp8"):
                     row[f"hbm_{name}"] = n * k / (us[name] * 1e-6) / HBM_PEAK
+                if name.startswith("gemm"):
+                    row[f"mfma_{name}"] = (2.0 * m * n * k
+                                           / (us[name] * 1e-6) / MFMA_PEAK)
+                    row[f"vs_deq_{name}"] = us[name] / us["deq"]
+                if name not in ("w16", "w16b"):
                     row[f"ratio_{name}"] = us[name] / min(us["w16"],
                                                           us["w16b"])
             rows.append(row)
             print(json.dumps(row), flush=True)
         del w16, q
     if args.out:
-        names = [nm for nm in rows[0]["us"] if nm.startswith("fp8")]
         with open(args.out, "w") as f:
-            f.write("| N | K | M | 16-bit us | 16-bit again us | spread | "
-                    + " | ".join(f"{nm} us | hbm% | vs 16-bit" for nm in names)
-                    + " |\n")
-            f.write("|" + "---|" * (6 + 3 * len(names)) + "\n")
-            for r in rows:
-                cells = [r["n"], r["k"], r["m"], f"{r['us']['w16']:.1f}",
-                         f"{r['us']['w16b']:.1f}", f"{r['spread']:.1%}"]
+            # one table per column set: M <= 64 has no deq/gemm columns
+            for names in sorted({tuple(nm for nm in r["us"]
+                                       if nm not in ("w16", "w16b"))
+                                 for r in rows}, key=len):
+                head = []
                 for nm in names:
-                    cells += [f"{r['us'][nm]:.1f}", f"{r['hbm_' + nm]:.0%}",
-                              f"{r['ratio_' + nm]:.2f}"]
-                f.write("| " + " | ".join(str(c) for c in cells) + " |\n")
+                    head.append(f"{nm} us")
+                    if nm.startswith("fp8"):
+                        head.append("hbm%")
+                    if nm.startswith("gemm"):
+                        head += ["mfma%", "vs deq"]
+                    head.append("vs 16-bit")
+                f.write("| N | K | M | 16-bit us | 16-bit again us | spread | "
+                        + " | ".join(head) + " |\n")
+                f.write("|" + "---|" * (6 + len(head)) + "\n")
+                for r in rows:
+                    if tuple(nm for nm in r["us"]
+                             if nm not in ("w16", "w16b")) != names:
+                        continue
+                    cells = [r["n"], r["k"], r["m"], f"{r['us']['w16']:.1f}",
+                             f"{r['us']['w16b']:.1f}", f"{r['spread']:.1%}"]
+                    for nm in names:
+                        cells.append(f"{r['us'][nm]:.1f}")
+                        if nm.startswith("fp8"):
+                            cells.append(f"{r['hbm_' + nm]:.0%}")
+                        if nm.startswith("gemm"):
+                            cells += [f"{r['mfma_' + nm]:.1%}",
+                                      f"{r['vs_deq_' + nm]:.2f}"]
+                        cells.append(f"{r['ratio_' + nm]:.2f}")
+                    f.write("| " + " | ".join(str(c) for c in cells) + " |\n")
+                f.write("\n")
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ other, through ``generate(page_size=16)`` on the same model: Llama-2-7B
 shapes, random weights, bf16, pages of 16 tokens.
 
   python benchmarks/serving_bench.py [--layers 32] [--repeats 3]
+      [--weight-dtype fp8] [--fp8-gemm-max-m 64]
 
 Both variants are warmed with a short request first and then alternate
 --repeats times in one process; wall-clock time between device
@@ -39,6 +40,13 @@ def main():
     p.add_argument("--packed", action="store_true",
                    help="also time ContinuousBatcher(packed=True), "
                         "alternating with the padded engine")
+    p.add_argument("--weight-dtype", default="16bit", choices=["16bit", "fp8"],
+                   help="fp8: quantise the decoder projections to e4m3 "
+                        "weights (quantize_model_fp8) before serving")
+    p.add_argument("--fp8-gemm-max-m", type=int, default=None,
+                   help="with fp8 weights: override ops.linear_fp8."
+                        "FP8_GEMM_MAX_M; 64 sends every step above 64 rows "
+                        "down the dequantise path, as before fp8_gemm")
     args = p.parse_args()
 
     from torchacc_amd.models import (ContinuousBatcher, LlamaForCausalLM,
@@ -50,6 +58,11 @@ def main():
     cfg.num_hidden_layers = args.layers
     with torch.device("cuda"):
         model = LlamaForCausalLM(cfg).to(torch.bfloat16).eval()
+    if args.weight_dtype == "fp8":
+        from torchacc_amd.ops import linear_fp8
+        linear_fp8.quantize_model_fp8(model)
+        if args.fp8_gemm_max_m is not None:
+            linear_fp8.FP8_GEMM_MAX_M = args.fp8_gemm_max_m
     gen = torch.Generator().manual_seed(0)
     lens = [int(x) for x in torch.linspace(16, 1024, REQUESTS).round()]
     order = torch.randperm(REQUESTS, generator=gen).tolist()
@@ -91,6 +104,8 @@ def main():
     line = {"model": "llama-2-7b", "layers": args.layers, "requests": REQUESTS,
             "prompt_lens": "16..1024", "new_tokens": NEW, "page": PAGE,
             "max_batch": MAX_BATCH, "prefill_chunk": args.prefill_chunk,
+            "weight_dtype": args.weight_dtype,
+            "fp8_gemm_max_m": args.fp8_gemm_max_m,
             "tokens_agree": f"{agree}/{REQUESTS * NEW}"}
     for name in fns:
         line[f"{name}_tok_s"] = round(statistics.median(samples[name]), 1)

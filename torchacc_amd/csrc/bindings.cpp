@@ -123,6 +123,10 @@ torch::Tensor fp8_linear(torch::Tensor x, torch::Tensor w8,
                          torch::Tensor scale,
                          c10::optional<torch::Tensor> bias, long num_splits);
 long fp8_linear_num_splits(long n, long k, long num_cus);
+// tiled variant for M > 64; num_splits: 0 = chosen from (M, N, K), CU count
+torch::Tensor fp8_gemm(torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
+                       c10::optional<torch::Tensor> bias, long num_splits);
+long fp8_gemm_num_splits(long m, long n, long k, long num_cus);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torchacc_amd CDNA4 (gfx950) kernels";
@@ -158,4 +162,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("scale"), pybind11::arg("bias") = pybind11::none(),
         pybind11::arg("num_splits") = 0);
   m.def("fp8_linear_num_splits", &fp8_linear_num_splits);
+  m.def("fp8_gemm", &fp8_gemm, pybind11::arg("x"), pybind11::arg("w8"),
+        pybind11::arg("scale"), pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("num_splits") = 0);
+  m.def("fp8_gemm_num_splits", &fp8_gemm_num_splits);
 }

@@ -37,6 +37,12 @@
 // bytes, so an LDS stage could not cut the traffic and would put a barrier
 // per chunk on the weight stream (profiles/r15_fp8_linear.md). Rows >= M are
 // read from row M-1 and never stored, so the MFMA path has no predicate.
+//
+// M > 64 (prefill, mixed serving steps) is served by fp8_gemm further down, a
+// 128 x 128 tiled kernel on the 32x32x16 MFMA that stages both operands in
+// LDS. It is bitwise repeatable and depends on (M, N, K, CU count) only, but
+// its K split depends on M: the batch invariance above holds for fp8_linear
+// (M <= 64) alone.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -285,6 +291,236 @@ void fp8_linear_combine_kernel(const float* __restrict__ part,
   fp8l_finish4<FP16>(v, m, n, N, scale, bias, y);
 }
 
+// ---------------------------------------------------------------------------
+// fp8_gemm: the same formula for M > 64 (prefill, mixed serving steps), as a
+// tiled GEMM that reads every code once per row tile and converts it once.
+//
+// A workgroup of 4 waves computes 128 x rows by 128 channels over BK = 64
+// steps; the waves sit 2 (channels) x 2 (rows), each on 64 x 64 as 2 x 2 tiles
+// of v_mfma_f32_32x32x16_{bf16,f16}. As in the skinny kernel the WEIGHTS are
+// the A operand, so the result is y^T: lane l owns x row l&31 of a tile and,
+// per group of four accumulator registers q, the four consecutive channels
+// 8q + 4(l>>5)..+3: the epilogue is fp8l_finish4.
+//
+// LDS: two stages of (x image, weight image), both [128 rows][64 x 16 bit]
+// row-major with 128-byte rows whose eight 16-byte chunks are XORed with
+// (row>>1)&7, 16 KiB each, 64 KiB in all (two workgroups per CU). A lane's A
+// or B fragment of K-step kk is chunk 2kk + (l>>5) of row l&31: one
+// ds_read_b128, and 16 consecutive lanes (rows 16n..16n+15, one chunk) touch
+// the 16 distinct 16-byte slots of the 256-byte bank line.
+//   x goes global -> LDS directly (attn_glds16); a wave instruction fills 64
+//   consecutive slots (8 rows), and the swizzle goes on the source address.
+//   Rows >= M read row M-1 and are never stored.
+//   Weights: a thread loads 2 x 16 codes of stage t+1 before the MFMAs of
+//   stage t, converts them after those MFMAs (fp8l_cvt8, exact) and writes
+//   them as 16-bit chunks with ds_write_b128: every code is converted once
+//   per workgroup. Channels >= N read row N-1 and are predicated at the store.
+//   One barrier per stage. The ragged step (K % 64 != 0) is always the last
+//   one: it stages x through registers so that 16-code granules at or past K
+//   are zero in both operands.
+//
+// Filling the device: where the tiles are fewer than the CUs, K is cut over
+// S workgroups (grid.z) that write fp32 partials [S][M][N], summed in split
+// order by fp8_linear_combine_kernel. No atomics: results are bitwise
+// repeatable and depend on (M, N, K, CU count) only. S depends on M, so unlike
+// the skinny kernel this path does NOT promise that a row's bits are
+// independent of the batch it sits in.
+constexpr int FP8G_BM = 128;      // x rows per workgroup
+constexpr int FP8G_BN = 128;      // channels per workgroup
+constexpr int FP8G_BK = 64;
+constexpr int FP8G_TILE_B = 128 * FP8G_BK * 2;     // one 16-bit image
+constexpr int FP8G_STAGE_B = 2 * FP8G_TILE_B;      // x image, weight image
+constexpr int FP8G_MAX_SPLITS = 16;
+// BK steps a split keeps at least when S is chosen automatically: prologue,
+// epilogue and the partials' traffic are paid per split
+constexpr int FP8G_MIN_STEPS = 4;
+static_assert(FP8G_BM == FP8G_BN, "both images share fp8g_off");
+
+// byte offset of 16-byte chunk ch (0..7) of row `row` in an image
+DEVINLINE constexpr unsigned fp8g_off(int row, int ch) {
+  return (unsigned)(row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
+}
+
+template <bool FP16>
+DEVINLINE f32x16 fp8g_mfma(attn_u32x4 a, attn_u32x4 b, f32x16 c) {
+  if constexpr (FP16) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(
+        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
+        c, 0, 0, 0);
+  } else {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+        __builtin_bit_cast(fp8l_bf16x8, a), __builtin_bit_cast(fp8l_bf16x8, b),
+        c, 0, 0, 0);
+  }
+}
+
+// Wait for this wave's direct-to-LDS loads (counted on vmcnt; 0x0F70 is
+// vmcnt(0) alone), then a workgroup barrier with its LDS fences written out:
+// __syncthreads() is a call here, once per BK step.
+DEVINLINE void fp8g_publish() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// grid = (ceil(N/128), ceil(M/128), S); block = 256.
+// S == 1: writes y. S > 1: writes raw fp32 sums to part[S][M][N].
+template <bool FP16>
+__global__ __launch_bounds__(256, 2)
+void fp8_gemm_kernel(const short* __restrict__ x,
+                     const unsigned char* __restrict__ w,
+                     const float* __restrict__ scale,
+                     const short* __restrict__ bias,
+                     short* __restrict__ y, float* __restrict__ part,
+                     int M, int N, int K) {
+  __shared__ __attribute__((aligned(16))) char lds[2 * FP8G_STAGE_B];
+  const int tid = threadIdx.x, lane = tid % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int wn = wave & 1, wm = wave >> 1;
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int n0 = blockIdx.x * FP8G_BN, m0 = blockIdx.y * FP8G_BM;
+  const int split = blockIdx.z, S = gridDim.z;
+
+  // contiguous, balanced runs of BK steps over the splits; the host keeps
+  // S <= T, so every split owns at least one step
+  const int T = (K + FP8G_BK - 1) / FP8G_BK, Tfull = K / FP8G_BK;
+  const int t0 = (int)((long)split * T / S);
+  const int t1 = (int)((long)(split + 1) * T / S);
+
+  // x staging: pass i fills slots i*256 + tid of the image, slot s = row
+  // s>>3, stored chunk s&7, which holds logical chunk (s&7) ^ ((row>>1)&7);
+  // the row's bits 1..3 are tid's bits 4..6 in every pass
+  const int xc = (tid & 7) ^ ((tid >> 4) & 7);
+  const short* xsrc[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    xsrc[i] = x + (long)min(m0 + i * 32 + (tid >> 3), M - 1) * K + xc * 8;
+  // weight staging: pass i, row i*64 + tid>>2, codes 16*(tid&3)..+15 of the
+  // step, i.e. 16-bit chunks 2*(tid&3) and the next one
+  const int wq = tid & 3;
+  const unsigned char* wsrc[2];
+  unsigned wdst[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = i * 64 + (tid >> 2);
+    wsrc[i] = w + (long)min(n0 + row, N - 1) * K + wq * 16;
+    wdst[i] = FP8G_TILE_B + fp8g_off(row, 2 * wq);
+  }
+
+  // issue the loads of step t: x into buffer `buf`, the codes into wv
+  auto stage_load = [&](int t, int buf, attn_u32x4 (&wv)[2]) {
+    const int k0 = t * FP8G_BK;
+    const bool tail = t >= Tfull;
+    char* xi = lds + buf * FP8G_STAGE_B;
+    if (!tail) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        attn_glds16(xsrc[i] + k0, xi + (i * 256 + wave * WAVE) * 16);
+    } else {
+      const bool live = k0 + xc * 8 < K;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        attn_u32x4 v = attn_u32x4{0u, 0u, 0u, 0u};
+        if (live) v = *reinterpret_cast<const attn_u32x4*>(xsrc[i] + k0);
+        *reinterpret_cast<attn_u32x4*>(xi + (i * 256 + tid) * 16) = v;
+      }
+    }
+    const bool wlive = !tail || k0 + wq * 16 < K;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      wv[i] = attn_u32x4{0u, 0u, 0u, 0u};
+      if (wlive) wv[i] = *reinterpret_cast<const attn_u32x4*>(wsrc[i] + k0);
+    }
+  };
+  // convert the 32 codes and write them into buffer `buf`
+  auto stage_commit = [&](int buf, const attn_u32x4 (&wv)[2]) {
+    char* base = lds + buf * FP8G_STAGE_B;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      *reinterpret_cast<attn_u32x4*>(base + wdst[i]) =
+          fp8l_cvt8<FP16>(wv[i][0], wv[i][1]);
+      *reinterpret_cast<attn_u32x4*>(base + (wdst[i] ^ 16u)) =
+          fp8l_cvt8<FP16>(wv[i][2], wv[i][3]);
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  attn_u32x4 wv[2];
+  stage_load(t0, 0, wv);
+  stage_commit(0, wv);
+  fp8g_publish();
+
+  // fragment reads: row 32*tile + l31 of the wave's half, chunk 2kk + hi
+  const unsigned sw = (unsigned)((l31 >> 1) & 7);
+  const unsigned xrow_off = (unsigned)((wm * 64 + l31) * 128);
+  const unsigned wrow_off = (unsigned)(FP8G_TILE_B + (wn * 64 + l31) * 128);
+
+  for (int t = t0; t < t1; ++t) {
+    const int cur = (t - t0) & 1;
+    const bool more = t + 1 < t1;
+    // buffer cur^1 was last read before the barrier that ended step t-1
+    if (more) stage_load(t + 1, cur ^ 1, wv);
+    const char* base = lds + cur * FP8G_STAGE_B;
+#pragma unroll
+    for (int kk = 0; kk < FP8G_BK / 16; ++kk) {
+      const unsigned ch = (((unsigned)(2 * kk + hi)) ^ sw) << 4;
+      attn_u32x4 a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        a[i] = *reinterpret_cast<const attn_u32x4*>(
+            base + wrow_off + i * (32 * 128) + ch);
+        b[i] = *reinterpret_cast<const attn_u32x4*>(
+            base + xrow_off + i * (32 * 128) + ch);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = fp8g_mfma<FP16>(a[i], b[j], acc[i][j]);
+    }
+    if (more) stage_commit(cur ^ 1, wv);
+    // publishes buffer cur^1 and retires this step's reads of buffer cur
+    fp8g_publish();
+  }
+
+  // lane: x row m of tile j; registers 4q..4q+3 of tile i: channels n..n+3
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = m0 + wm * 64 + j * 32 + l31;
+    if (m >= M) continue;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + wn * 64 + i * 32 + 8 * q + 4 * hi;
+        if (n >= N) continue;
+        const f32x4 v = f32x4{acc[i][j][4 * q], acc[i][j][4 * q + 1],
+                              acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+        if (S == 1) {
+          fp8l_finish4<FP16>(v, m, n, N, scale, bias, y);
+        } else {
+          float* p = part + ((long)split * M + m) * N + n;
+          if ((N & 3) == 0) {
+            *reinterpret_cast<f32x4*>(p) = v;
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (n + r < N) p[r] = v[r];
+          }
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 #pragma clang attribute pop
@@ -377,6 +613,103 @@ torch::Tensor fp8_linear(torch::Tensor x, torch::Tensor w8,
     else FP8L_LAUNCH(4);
   });
 #undef FP8L_LAUNCH
+  HIP_CHECK_LAST();
+  if (S > 1) {
+    const long groups = M * ((N + 3) / 4);
+    FP16_SWITCH(fp16, {
+      hipLaunchKernelGGL((fp8_linear_combine_kernel<kFP16>),
+                         dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+                         stream, part_p, scale.data_ptr<float>(), bias_p,
+                         (short*)y.data_ptr(), (int)M, (int)N, (int)S);
+    });
+    HIP_CHECK_LAST();
+  }
+  return y;
+}
+
+// Number of K splits of fp8_gemm for an [M, K] x [N, K]^T problem on a device
+// with num_cus compute units: 1 once the 128 x 128 tiles cover the CUs,
+// otherwise as many as bring the workgroup count up to the CU count, while
+// every split keeps at least FP8G_MIN_STEPS whole BK steps (one, where K has
+// fewer than that).
+long fp8_gemm_num_splits(long m, long n, long k, long num_cus) {
+  const long tiles =
+      ((m + FP8G_BM - 1) / FP8G_BM) * ((n + FP8G_BN - 1) / FP8G_BN);
+  const long steps = k / FP8G_BK;   // whole steps
+  const long want = num_cus / tiles;
+  const long cap = std::min<long>(FP8G_MAX_SPLITS, steps / FP8G_MIN_STEPS);
+  return std::max<long>(1, std::min(want, cap));
+}
+
+// y = (x @ dequant(w8)^T) * scale (+ bias) for any M >= 1, on the tiled
+// kernel. num_splits: 0 = chosen from (M, N, K) and the CU count, otherwise
+// forced (benchmarks, tests).
+torch::Tensor fp8_gemm(torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
+                       c10::optional<torch::Tensor> bias, long num_splits) {
+  TORCH_CHECK(x.is_cuda() && w8.is_cuda() && scale.is_cuda(),
+              "fp8_gemm: GPU tensors required");
+  TORCH_CHECK(x.dim() == 2 && w8.dim() == 2 && scale.dim() == 1,
+              "fp8_gemm: x [M,K], w8 [N,K], scale [N]");
+  const bool fp16 = x.scalar_type() == torch::kHalf;
+  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
+              "fp8_gemm: x must be bf16 or fp16");
+  TORCH_CHECK(w8.scalar_type() == torch::kFloat8_e4m3fn,
+              "fp8_gemm: w8 must be float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat,
+              "fp8_gemm: scale must be fp32");
+  TORCH_CHECK(x.is_contiguous() && w8.is_contiguous() && scale.is_contiguous(),
+              "fp8_gemm: contiguous operands");
+  TORCH_CHECK(w8.device() == x.device() && scale.device() == x.device(),
+              "fp8_gemm: operands on different devices");
+  const long M = x.size(0), K = x.size(1), N = w8.size(0);
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 16 && K % 16 == 0,
+              "fp8_gemm: K must be a positive multiple of 16");
+  TORCH_CHECK(w8.size(1) == K && scale.size(0) == N,
+              "fp8_gemm: shape mismatch");
+  TORCH_CHECK(M * K < (1L << 31) && (M + FP8G_BM) * N < (1L << 31) &&
+                  (M + FP8G_BM - 1) / FP8G_BM <= 65535,
+              "fp8_gemm: problem too large");
+  const short* bias_p = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                    bias->scalar_type() == x.scalar_type() &&
+                    bias->dim() == 1 && bias->size(0) == N &&
+                    bias->is_contiguous(),
+                "fp8_gemm: bias must be [N], contiguous, x's dtype/device");
+    bias_p = (const short*)bias->data_ptr();
+    TORCH_CHECK((uintptr_t)bias_p % 8 == 0, "fp8_gemm: bias alignment");
+  }
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)w8.data_ptr() % 16 == 0 &&
+                  (uintptr_t)scale.data_ptr() % 16 == 0,
+              "fp8_gemm: operands must be 16-byte aligned");
+
+  long S = num_splits;
+  if (S <= 0) {
+    S = fp8_gemm_num_splits(
+        M, N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+  }
+  TORCH_CHECK(S <= FP8G_MAX_SPLITS, "fp8_gemm: num_splits above ",
+              FP8G_MAX_SPLITS);
+  // every split keeps at least one whole BK step
+  S = std::max<long>(1, std::min(S, K / FP8G_BK));
+
+  auto y = torch::empty({M, N}, x.options());
+  torch::Tensor part;
+  float* part_p = nullptr;
+  if (S > 1) {
+    part = torch::empty({S, M, N}, x.options().dtype(torch::kFloat));
+    part_p = part.data_ptr<float>();
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  const dim3 grid((N + FP8G_BN - 1) / FP8G_BN, (M + FP8G_BM - 1) / FP8G_BM, S);
+  FP16_SWITCH(fp16, {
+    hipLaunchKernelGGL((fp8_gemm_kernel<kFP16>), grid, dim3(256), 0, stream,
+                       (const short*)x.data_ptr(),
+                       (const unsigned char*)w8.data_ptr(),
+                       scale.data_ptr<float>(), bias_p, (short*)y.data_ptr(),
+                       part_p, (int)M, (int)N, (int)K);
+  });
   HIP_CHECK_LAST();
   if (S > 1) {
     const long groups = M * ((N + 3) / 4);

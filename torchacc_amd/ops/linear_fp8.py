@@ -6,7 +6,10 @@ the weight memory that competes with KV pages); activations stay 16-bit. The
 only approximation is the one-off weight rounding in
 ``quantize_weight_fp8``: ``fp8_linear`` computes
 ``(x @ codes^T) * scale + bias`` with fp32 accumulation, on the
-``_C.fp8_linear`` MFMA kernel (csrc/fp8_linear.hip) for decode-sized batches.
+``_C.fp8_linear`` MFMA kernel (csrc/fp8_linear.hip) for decode-sized batches
+and on the tiled ``_C.fp8_gemm`` kernel of the same file above them (prefill,
+mixed serving steps): through ``FP8_GEMM_MAX_M`` rows the weight is never
+dequantised in memory on a GPU.
 
 Inference only.
 """
@@ -20,8 +23,8 @@ from .linear import TunedLinear, tuned_linear
 
 E4M3_MAX = 448.0
 
-# Rows up to which GPU inputs take the fp8 kernel; above it (prefill,
-# compute-bound) the weight is dequantised and the 16-bit GEMM runs.
+# Rows up to which GPU inputs take the skinny fp8 kernel; above it (prefill,
+# compute-bound) the tiled fp8_gemm kernel runs, see FP8_GEMM_MAX_M.
 # Measured (profiles/r15_fp8_linear.md): against the 16-bit GEMM on resident
 # 16-bit weights the kernel wins through M = 16 at every projection shape,
 # at M = 32 except the 11008/14336 x 4096 shapes (1.2x), and is 1.04-1.73x
@@ -29,6 +32,18 @@ E4M3_MAX = 448.0
 # alternative here also has to dequantise N*K weights per call (not timed),
 # so the kernel keeps M <= 64.
 FP8_LINEAR_MAX_M = 64
+
+# Rows up to which GPU inputs above FP8_LINEAR_MAX_M take the tiled fp8_gemm
+# kernel; None = no upper limit. Beyond it the weight is dequantised in
+# memory and the 16-bit GEMM runs (the only path there before fp8_gemm).
+# Measured (profiles/r16_fp8_gemm.md, eight projection / LM-head shapes, time
+# of fp8_gemm over time of the dequantise path, run-to-run spread <= 3%):
+# M = 128: 0.07-0.42, 256: 0.13-0.54, 512: 0.23-0.48, 1024: 0.41-0.54,
+# 2048: 0.56-0.74, 4096: 0.75-1.07 (slower at 128256 x 4096 and 1024 x 4096,
+# level at 32000 x 4096). 2048 is the largest benchmarked M at which the
+# kernel wins at every shape. The dequantise path also allocates two fp32
+# N*K transients per call (4008 MiB for the 128256 x 4096 head).
+FP8_GEMM_MAX_M = 2048
 
 
 def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -46,7 +61,11 @@ def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def fp8_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
                bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``(x @ w8.float().T) * scale + bias`` in ``x.dtype``; x [..., K]."""
+    """``(x @ w8.float().T) * scale + bias`` in ``x.dtype``; x [..., K].
+
+    On a GPU the result is bitwise repeatable. Up to ``FP8_LINEAR_MAX_M`` rows
+    a row's bits also do not depend on the batch it sits in; above it (the
+    tiled kernel, whose K split depends on M) that is not promised."""
     if torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (x, scale, bias)):
         raise RuntimeError(
@@ -62,6 +81,8 @@ def fp8_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
         out = out.to(x.dtype)
     elif x2d.shape[0] <= FP8_LINEAR_MAX_M:
         out = ext.fp8_linear(x2d.contiguous(), w8, scale, bias)
+    elif FP8_GEMM_MAX_M is None or x2d.shape[0] <= FP8_GEMM_MAX_M:
+        out = ext.fp8_gemm(x2d.contiguous(), w8, scale, bias)
     else:
         w = (w8.float() * scale[:, None]).to(x.dtype)
         out = tuned_linear(x2d, w, bias)
