@@ -37,6 +37,9 @@ def main():
                         "(quantize_model_fp8; default: 16-bit weights)")
     p.add_argument("--fp8-lm-head", action="store_true",
                    help="with --weight-dtype fp8: quantise lm_head too")
+    p.add_argument("--fp8-one-launch", action="store_true",
+                   help="with --weight-dtype fp8: one-launch projections and "
+                        "the fused gate/up SwiGLU MLP (one_launch=True)")
     args = p.parse_args()
     gen_kw = {"kv_dtype": args.kv_dtype}
     if args.page_size is not None:
@@ -60,7 +63,8 @@ def main():
         model = LlamaForCausalLM(mcfg).eval()
     if args.weight_dtype == "fp8":
         from torchacc_amd.ops import quantize_model_fp8
-        quantize_model_fp8(model, include_lm_head=args.fp8_lm_head)
+        quantize_model_fp8(model, include_lm_head=args.fp8_lm_head,
+                           one_launch=args.fp8_one_launch)
     ids = torch.randint(0, mcfg.vocab_size, (args.batch, args.prompt),
                         device=dev)
 
@@ -87,6 +91,8 @@ def main():
     if args.weight_dtype is not None:
         extra = {"weight_dtype": args.weight_dtype,
                  "fp8_lm_head": args.fp8_lm_head}
+        if args.fp8_one_launch:
+            extra["fp8_one_launch"] = True
     print(json.dumps({
         "metric": "decode tokens/sec",
         "value": new_tokens / (t1 - t0),

@@ -127,6 +127,19 @@ long fp8_linear_num_splits(long n, long k, long num_cus);
 torch::Tensor fp8_gemm(torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
                        c10::optional<torch::Tensor> bias, long num_splits);
 long fp8_gemm_num_splits(long m, long n, long k, long num_cus);
+// one-launch kernels for M <= 64; waves / tiles: 0 = fp8_wide_instance's pick
+torch::Tensor fp8_linear_wide(torch::Tensor x, torch::Tensor w8,
+                              torch::Tensor scale,
+                              c10::optional<torch::Tensor> bias, long waves,
+                              long tiles);
+torch::Tensor fp8_swiglu_linear(torch::Tensor x, torch::Tensor wg8,
+                                torch::Tensor sg, torch::Tensor wu8,
+                                torch::Tensor su,
+                                c10::optional<torch::Tensor> bias_gate,
+                                c10::optional<torch::Tensor> bias_up,
+                                long waves);
+std::vector<long> fp8_wide_instance(long n, long k, long num_cus,
+                                    bool swiglu);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torchacc_amd CDNA4 (gfx950) kernels";
@@ -166,4 +179,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("scale"), pybind11::arg("bias") = pybind11::none(),
         pybind11::arg("num_splits") = 0);
   m.def("fp8_gemm_num_splits", &fp8_gemm_num_splits);
+  m.def("fp8_linear_wide", &fp8_linear_wide, pybind11::arg("x"),
+        pybind11::arg("w8"), pybind11::arg("scale"),
+        pybind11::arg("bias") = pybind11::none(), pybind11::arg("waves") = 0,
+        pybind11::arg("tiles") = 0);
+  m.def("fp8_swiglu_linear", &fp8_swiglu_linear, pybind11::arg("x"),
+        pybind11::arg("wg8"), pybind11::arg("sg"), pybind11::arg("wu8"),
+        pybind11::arg("su"), pybind11::arg("bias_gate") = pybind11::none(),
+        pybind11::arg("bias_up") = pybind11::none(),
+        pybind11::arg("waves") = 0);
+  m.def("fp8_wide_instance", &fp8_wide_instance);
 }

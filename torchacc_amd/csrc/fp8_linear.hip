@@ -38,6 +38,10 @@
 // per chunk on the weight stream (profiles/r15_fp8_linear.md). Rows >= M are
 // read from row M-1 and never stored, so the MFMA path has no predicate.
 //
+// fp8_wide further down is the same body in one launch for every (N, K): K is
+// cut only across the 4 or 8 waves of a workgroup on 16 or 32 channels, with
+// a plain epilogue and a fused gate/up SwiGLU one (opt-in, one_launch=True).
+//
 // M > 64 (prefill, mixed serving steps) is served by fp8_gemm further down, a
 // 128 x 128 tiled kernel on the 32x32x16 MFMA that stages both operands in
 // LDS. It is bitwise repeatable and depends on (M, N, K, CU count) only, but
@@ -47,6 +51,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 #include "attn_common.h"
@@ -147,12 +152,13 @@ DEVINLINE void fp8l_finish4(f32x4 v, long m, int n, int N,
 // One 128-code step of a wave: for each half (64 codes) every lane loads its
 // 16 codes of both tiles and its 16 activations of every column block, then
 // 2 K-steps x NT x MT MFMAs. TAIL is the one ragged step at the end of K
-// (K % 128 != 0): 16-code granules at or past K contribute zeros.
-template <bool FP16, int MT, bool TAIL>
-DEVINLINE void fp8l_step(const unsigned char* const (&wrow)[FP8L_NT],
+// (K % 128 != 0): 16-code granules at or past K contribute zeros. NT is
+// deduced from the row pointers (2 everywhere but the one-tile wide kernel).
+template <bool FP16, int MT, bool TAIL, int NT>
+DEVINLINE void fp8l_step(const unsigned char* const (&wrow)[NT],
                          const short* const (&xrow)[MT], int kl, int K,
-                         f32x4 (&acc)[FP8L_NT][MT]) {
-  attn_u32x4 wv[2][FP8L_NT];
+                         f32x4 (&acc)[NT][MT]) {
+  attn_u32x4 wv[2][NT];
   attn_u32x4 xv[2][MT][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -160,7 +166,7 @@ DEVINLINE void fp8l_step(const unsigned char* const (&wrow)[FP8L_NT],
     const bool live = !TAIL || k < K;
     const int kc = live ? k : 0;
 #pragma unroll
-    for (int nt = 0; nt < FP8L_NT; ++nt) {
+    for (int nt = 0; nt < NT; ++nt) {
       wv[h][nt] = *reinterpret_cast<const attn_u32x4*>(wrow[nt] + kc);
       if (TAIL && !live) wv[h][nt] = attn_u32x4{0u, 0u, 0u, 0u};
     }
@@ -179,7 +185,7 @@ DEVINLINE void fp8l_step(const unsigned char* const (&wrow)[FP8L_NT],
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
 #pragma unroll
-      for (int nt = 0; nt < FP8L_NT; ++nt) {
+      for (int nt = 0; nt < NT; ++nt) {
         const attn_u32x4 a =
             fp8l_cvt8<FP16>(wv[h][nt][2 * s], wv[h][nt][2 * s + 1]);
 #pragma unroll
@@ -289,6 +295,138 @@ void fp8_linear_combine_kernel(const float* __restrict__ part,
     }
   }
   fp8l_finish4<FP16>(v, m, n, N, scale, bias, y);
+}
+
+// ---------------------------------------------------------------------------
+// fp8_wide: the skinny GEMM in ONE launch for every (N, K). At batch 1 a
+// layer's projections are bound by launch count, not bytes
+// (profiles/r17_fp8_one_launch.md), so K is never cut across workgroups: no
+// partials, no combine launch, no allocation besides y. The device is filled
+// from the other side instead: a workgroup is W in {4, 8} waves on only 16 or
+// 32 channels, each wave on its own contiguous, balanced run of 128-code
+// steps (fp8_linear_kernel's slot arithmetic with S = 1), and the W
+// accumulators are summed through LDS in wave order. W and NT are compile-time
+// instances picked from (N, K, CU count) alone, so no K boundary moves with
+// the batch; a row's bits are the same for every MT.
+//
+// Two epilogues on that body:
+//   PLAIN   y = acc * scale (+ bias); NT in {1, 2} tiles of one weight.
+//   SWIGLU  the wave's two tiles are tile i of the GATE weight and tile i of
+//           the UP weight (two pointers, two scale vectors, nothing
+//           interleaved): one x fragment feeds both, a workgroup owns 16
+//           channels of y = silu(g * sg (+ bg)) * (u * su (+ bu)). The two
+//           pre-activations stay fp32 in registers / LDS: they are never
+//           rounded to 16 bit and never reach memory.
+//
+// LDS: red[W][NT * MT][64] f32x4, at most 8 * 8 * 1 KiB = 64 KiB (W = 8,
+// NT = 2, MT = 4); after one barrier thread (i, l) sums slot (i, l) of waves
+// 0..W-1 in that order and runs the epilogue for its 4 channels of one row.
+// Tails as in fp8_linear_kernel: channels >= N read a clamped row and are
+// predicated at the store, rows >= M read row M-1 and are never stored, the
+// one ragged step zero-fills 16-code granules at or past K. M <= 64.
+
+// silu(g) * u for channels n..n+3 of row m; fp8l_finish4's store rule.
+template <bool FP16>
+DEVINLINE void fp8w_finish4_swiglu(f32x4 vg, f32x4 vu, long m, int n, int N,
+                                   const float* __restrict__ sg,
+                                   const float* __restrict__ su,
+                                   const short* __restrict__ bg,
+                                   const short* __restrict__ bu,
+                                   short* __restrict__ y) {
+  const bool vec = (N & 3) == 0;  // then n + 3 < N, 8-byte aligned row start
+  s16x4 ov;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int c = vec ? n + r : min(n + r, N - 1);
+    float g = vg[r] * sg[c], u = vu[r] * su[c];
+    if (bg != nullptr) g += AttnElem<FP16>::to_f32(bg[c]);
+    if (bu != nullptr) u += AttnElem<FP16>::to_f32(bu[c]);
+    // exp overflows to +inf for g < -88: the quotient is then -0, silu's limit
+    ov[r] = AttnElem<FP16>::from_f32(g / (1.f + __expf(-g)) * u);
+  }
+  if (vec) {
+    *reinterpret_cast<s16x4*>(y + m * N + n) = ov;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (n + r < N) y[m * N + n + r] = ov[r];
+  }
+}
+
+// grid = ceil(N / BN), BN = 16 (SWIGLU, or NT == 1) or 32; block = W * 64.
+// PLAIN reads (w0, s0, b0) only.
+template <bool FP16, int MT, int W, int NT, bool SWIGLU>
+__global__ __launch_bounds__(W * WAVE)
+void fp8_wide_kernel(const short* __restrict__ x,
+                     const unsigned char* __restrict__ w0,
+                     const unsigned char* __restrict__ w1,
+                     const float* __restrict__ s0,
+                     const float* __restrict__ s1,
+                     const short* __restrict__ b0,
+                     const short* __restrict__ b1,
+                     short* __restrict__ y, int M, int N, int K) {
+  static_assert(!SWIGLU || NT == 2, "SWIGLU: one gate tile, one up tile");
+  static_assert(W * NT * MT * WAVE * sizeof(f32x4) <= 64 * 1024, "LDS");
+  constexpr int BN = SWIGLU ? 16 : 16 * NT;
+  __shared__ f32x4 red[W][NT * MT][WAVE];
+  const int tid = threadIdx.x, lane = tid % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int j = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * BN;
+
+  // contiguous, balanced runs of steps over the W waves
+  const int T = (K + FP8L_STEP - 1) / FP8L_STEP, Tfull = K / FP8L_STEP;
+  const int t0 = (int)((long)wave * T / W);
+  const int t1 = (int)((long)(wave + 1) * T / W);
+
+  const unsigned char* wrow[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    if (SWIGLU)
+      wrow[nt] = (nt == 0 ? w0 : w1) + (long)min(n0 + j, N - 1) * K;
+    else
+      wrow[nt] = w0 + (long)min(n0 + nt * 16 + j, N - 1) * K;
+  }
+  const short* xrow[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+    xrow[mt] = x + (long)min(mt * 16 + j, M - 1) * K;
+
+  f32x4 acc[NT][MT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int tm = min(t1, Tfull);
+#pragma unroll 2
+  for (int t = t0; t < tm; ++t)
+    fp8l_step<FP16, MT, false>(wrow, xrow, t * FP8L_STEP + g * 16, K, acc);
+  if (t1 > Tfull)  // only the last wave, only when K % 128 != 0
+    fp8l_step<FP16, MT, true>(wrow, xrow, Tfull * FP8L_STEP + g * 16, K, acc);
+
+#pragma unroll
+  for (int i = 0; i < NT * MT; ++i) red[wave][i][lane] = acc[i / MT][i % MT];
+  __syncthreads();
+  // SWIGLU: one item per (column block, lane) takes the gate and the up sum
+  constexpr int ITEMS = (SWIGLU ? 1 : NT) * MT * WAVE;
+  for (int idx = tid; idx < ITEMS; idx += W * WAVE) {
+    const int i = idx / WAVE, l = idx % WAVE;
+    const int m = (i % MT) * 16 + (l & 15);
+    const int n = n0 + (i / MT) * 16 + 4 * (l >> 4);
+    if (m >= M || n >= N) continue;
+    f32x4 v = red[0][i][l];
+#pragma unroll
+    for (int wv = 1; wv < W; ++wv) v += red[wv][i][l];
+    if constexpr (SWIGLU) {
+      f32x4 u = red[0][MT + i][l];
+#pragma unroll
+      for (int wv = 1; wv < W; ++wv) u += red[wv][MT + i][l];
+      fp8w_finish4_swiglu<FP16>(v, u, m, n, N, s0, s1, b0, b1, y);
+    } else {
+      fp8l_finish4<FP16>(v, m, n, N, s0, b0, y);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -722,4 +860,154 @@ torch::Tensor fp8_gemm(torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
     HIP_CHECK_LAST();
   }
   return y;
+}
+
+// ---------------------------------------------------------------------------
+// fp8_wide host side.
+
+// The (W, NT) instance of the one-launch kernel for an [N, K] weight (SWIGLU:
+// N = I, a gate/up pair) on a device with num_cus compute units. A function
+// of (N, K, num_cus) only, never of M. Set by the sweep in
+// profiles/r17_fp8_one_launch.md: PLAIN takes 4 waves on two tiles (which
+// share one x fragment) once every CU gets a workgroup that way, and below
+// that 8 waves on one tile; 8 x 2 was never the fastest. SWIGLU (always two
+// tiles, 16 channels) takes 4 waves where that gives FP8W_WAVES_PER_CU waves
+// per CU, otherwise 8. W = 8 needs 8 steps in K, so that every wave keeps a
+// whole one.
+constexpr long FP8W_WAVES_PER_CU = 4 * FP8L_WG_PER_CU;
+
+std::vector<long> fp8_wide_instance(long n, long k, long num_cus,
+                                    bool swiglu) {
+  const long steps = (k + FP8L_STEP - 1) / FP8L_STEP;
+  const long wg16 = (n + 15) / 16, wg32 = (n + 31) / 32;
+  const long w8 = steps >= 8 ? 8 : 4;
+  if (swiglu) return {wg16 * 4 >= FP8W_WAVES_PER_CU * num_cus ? 4 : w8, 2};
+  if (wg32 >= num_cus) return {4, 2};
+  return {w8, 1};
+}
+
+namespace {
+
+// one (weight, scale, bias) triple of a wide call against x [M, K]
+void fp8w_check(const char* op, const torch::Tensor& x,
+                const torch::Tensor& w8, const torch::Tensor& scale,
+                const c10::optional<torch::Tensor>& bias) {
+  TORCH_CHECK(w8.is_cuda() && scale.is_cuda() && w8.device() == x.device() &&
+                  scale.device() == x.device(),
+              op, ": weights and scales on x's GPU required");
+  TORCH_CHECK(w8.dim() == 2 && scale.dim() == 1 &&
+                  w8.scalar_type() == torch::kFloat8_e4m3fn &&
+                  scale.scalar_type() == torch::kFloat,
+              op, ": w8 [N,K] float8_e4m3fn, scale [N] fp32");
+  TORCH_CHECK(w8.is_contiguous() && scale.is_contiguous() &&
+                  w8.size(1) == x.size(1) && scale.size(0) == w8.size(0),
+              op, ": contiguous operands of matching shape");
+  TORCH_CHECK((uintptr_t)w8.data_ptr() % 16 == 0 &&
+                  (uintptr_t)scale.data_ptr() % 16 == 0,
+              op, ": operands must be 16-byte aligned");
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                    bias->scalar_type() == x.scalar_type() &&
+                    bias->dim() == 1 && bias->size(0) == w8.size(0) &&
+                    bias->is_contiguous() &&
+                    (uintptr_t)bias->data_ptr() % 8 == 0,
+                op, ": bias must be [N], contiguous, aligned, x's dtype");
+  }
+}
+
+// Shared front end: PLAIN when w1 is absent, SWIGLU otherwise.
+torch::Tensor fp8_wide(const char* op, torch::Tensor x, torch::Tensor w0,
+                       torch::Tensor s0, c10::optional<torch::Tensor> b0,
+                       const torch::Tensor* w1, const torch::Tensor* s1,
+                       c10::optional<torch::Tensor> b1, long waves,
+                       long tiles) {
+  const bool swiglu = w1 != nullptr;
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+                  (uintptr_t)x.data_ptr() % 16 == 0,
+              op, ": x must be a contiguous, aligned [M,K] GPU tensor");
+  const bool fp16 = x.scalar_type() == torch::kHalf;
+  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
+              op, ": x must be bf16 or fp16");
+  fp8w_check(op, x, w0, s0, b0);
+  if (swiglu) {
+    fp8w_check(op, x, *w1, *s1, b1);
+    TORCH_CHECK(w1->size(0) == w0.size(0), op, ": gate/up shape mismatch");
+  }
+  const long M = x.size(0), K = x.size(1), N = w0.size(0);
+  TORCH_CHECK(M >= 1 && M <= 64, op, ": 1 <= M <= 64");
+  TORCH_CHECK(N >= 1 && K >= 16 && K % 16 == 0,
+              op, ": K must be a positive multiple of 16");
+  TORCH_CHECK(64 * K < (1L << 31) && 128 * N < (1L << 31),
+              op, ": problem too large");
+
+  const auto inst = fp8_wide_instance(
+      N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
+      swiglu);
+  const long W = waves > 0 ? waves : inst[0];
+  const long NT = swiglu ? 2 : (tiles > 0 ? tiles : inst[1]);
+  TORCH_CHECK((W == 4 || W == 8) && (NT == 1 || NT == 2),
+              op, ": instances are waves in {4, 8}, tiles in {1, 2}");
+
+  auto y = torch::empty({M, N}, x.options());
+  auto stream = at::hip::getCurrentHIPStream();
+  const long bn = swiglu ? 16 : 16 * NT;
+  const dim3 grid((unsigned)((N + bn - 1) / bn)), block((unsigned)(W * WAVE));
+  const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
+  auto bp = [](const c10::optional<torch::Tensor>& b) {
+    return b.has_value() ? (const short*)b->data_ptr() : nullptr;
+  };
+#define FP8W_LAUNCH(MTV, WV, NTV, SW)                                        \
+  hipLaunchKernelGGL((fp8_wide_kernel<kFP16, MTV, WV, NTV, SW>), grid,       \
+                     block, 0, stream, (const short*)x.data_ptr(),           \
+                     (const unsigned char*)w0.data_ptr(),                    \
+                     SW ? (const unsigned char*)w1->data_ptr() : nullptr,    \
+                     s0.data_ptr<float>(),                                   \
+                     SW ? s1->data_ptr<float>() : nullptr, bp(b0), bp(b1),   \
+                     (short*)y.data_ptr(), (int)M, (int)N, (int)K)
+#define FP8W_INSTANCE(MTV)                                  \
+  do {                                                      \
+    if (swiglu) {                                           \
+      if (W == 4) FP8W_LAUNCH(MTV, 4, 2, true);             \
+      else FP8W_LAUNCH(MTV, 8, 2, true);                    \
+    } else if (NT == 1) {                                   \
+      if (W == 4) FP8W_LAUNCH(MTV, 4, 1, false);            \
+      else FP8W_LAUNCH(MTV, 8, 1, false);                   \
+    } else {                                                \
+      if (W == 4) FP8W_LAUNCH(MTV, 4, 2, false);            \
+      else FP8W_LAUNCH(MTV, 8, 2, false);                   \
+    }                                                       \
+  } while (0)
+  FP16_SWITCH(fp16, {
+    if (mt == 1) FP8W_INSTANCE(1);
+    else if (mt == 2) FP8W_INSTANCE(2);
+    else FP8W_INSTANCE(4);
+  });
+#undef FP8W_INSTANCE
+#undef FP8W_LAUNCH
+  HIP_CHECK_LAST();
+  return y;
+}
+
+}  // namespace
+
+// fp8_linear's formula for M <= 64 in one launch whatever (N, K). waves /
+// tiles: 0 = fp8_wide_instance's choice, otherwise forced (benchmarks, tests).
+torch::Tensor fp8_linear_wide(torch::Tensor x, torch::Tensor w8,
+                              torch::Tensor scale,
+                              c10::optional<torch::Tensor> bias, long waves,
+                              long tiles) {
+  return fp8_wide("fp8_linear_wide", x, w8, scale, bias, nullptr, nullptr,
+                  c10::nullopt, waves, tiles);
+}
+
+// y[M,I] = silu((x @ dq(wg8)^T) * sg (+ bias_gate))
+//          * ((x @ dq(wu8)^T) * su (+ bias_up)), M <= 64, one launch.
+torch::Tensor fp8_swiglu_linear(torch::Tensor x, torch::Tensor wg8,
+                                torch::Tensor sg, torch::Tensor wu8,
+                                torch::Tensor su,
+                                c10::optional<torch::Tensor> bias_gate,
+                                c10::optional<torch::Tensor> bias_up,
+                                long waves) {
+  return fp8_wide("fp8_swiglu_linear", x, wg8, sg, bias_gate, &wu8, &su,
+                  bias_up, waves, 0);
 }

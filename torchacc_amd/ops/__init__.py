@@ -11,8 +11,9 @@ from .rope import apply_rotary_pos_emb, build_rope_cache  # noqa: F401
 from .swiglu import swiglu  # noqa: F401
 from .cross_entropy import cross_entropy, linear_cross_entropy  # noqa: F401
 from .adamw import AdamW  # noqa: F401
-from .linear_fp8 import (Fp8Linear, fp8_linear,  # noqa: F401
-                         quantize_model_fp8, quantize_weight_fp8)
+from .linear_fp8 import (Fp8Linear, Fp8SwiGLUMLP, fp8_linear,  # noqa: F401
+                         fp8_swiglu_linear, quantize_model_fp8,
+                         quantize_weight_fp8)
 from .scaled_dot_product_attention import scaled_dot_product_attention  # noqa: F401
 
 from . import context_parallel  # noqa: F401

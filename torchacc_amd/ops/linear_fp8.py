@@ -11,6 +11,11 @@ and on the tiled ``_C.fp8_gemm`` kernel of the same file above them (prefill,
 mixed serving steps): through ``FP8_GEMM_MAX_M`` rows the weight is never
 dequantised in memory on a GPU.
 
+Opt-in (``one_launch=True``): decode-sized batches take the one-launch
+kernels of the same file, ``_C.fp8_linear_wide`` and the fused gate/up
+``_C.fp8_swiglu_linear`` behind ``Fp8SwiGLUMLP``; a batch-1 step is bound by
+launch count, not bytes (profiles/r17_fp8_one_launch.md).
+
 Inference only.
 """
 from typing import Optional, Tuple
@@ -20,6 +25,7 @@ import torch.nn as nn
 
 from ._backend import dispatch
 from .linear import TunedLinear, tuned_linear
+from .swiglu import swiglu
 
 E4M3_MAX = 448.0
 
@@ -59,18 +65,28 @@ def quantize_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return w8.contiguous(), scale.contiguous()
 
 
+def _refuse_grad(op, *tensors):
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(
+            f"{op} is inference-only: call it under torch.no_grad() "
+            "or detach its inputs")
+
+
 def fp8_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
-               bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+               bias: Optional[torch.Tensor] = None,
+               one_launch: bool = False) -> torch.Tensor:
     """``(x @ w8.float().T) * scale + bias`` in ``x.dtype``; x [..., K].
 
     On a GPU the result is bitwise repeatable. Up to ``FP8_LINEAR_MAX_M`` rows
     a row's bits also do not depend on the batch it sits in; above it (the
-    tiled kernel, whose K split depends on M) that is not promised."""
-    if torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (x, scale, bias)):
-        raise RuntimeError(
-            "fp8_linear is inference-only: call it under torch.no_grad() "
-            "or detach its inputs")
+    tiled kernel, whose K split depends on M) that is not promised.
+
+    ``one_launch``: up to ``FP8_LINEAR_MAX_M`` rows take ``_C.fp8_linear_wide``
+    (K split inside the workgroup only: one launch, no partials) instead of
+    the kernel that may split K across workgroups and combine in a second
+    launch. Same properties, other summation order, so other last bits."""
+    _refuse_grad("fp8_linear", x, scale, bias)
     ext = dispatch(x)
     shape = x.shape
     x2d = x.reshape(-1, shape[-1])
@@ -80,7 +96,8 @@ def fp8_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
             out = out + bias.float()
         out = out.to(x.dtype)
     elif x2d.shape[0] <= FP8_LINEAR_MAX_M:
-        out = ext.fp8_linear(x2d.contiguous(), w8, scale, bias)
+        kernel = ext.fp8_linear_wide if one_launch else ext.fp8_linear
+        out = kernel(x2d.contiguous(), w8, scale, bias)
     elif FP8_GEMM_MAX_M is None or x2d.shape[0] <= FP8_GEMM_MAX_M:
         out = ext.fp8_gemm(x2d.contiguous(), w8, scale, bias)
     else:
@@ -89,48 +106,141 @@ def fp8_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
     return out.view(*shape[:-1], w8.shape[0])
 
 
+def fp8_swiglu_linear(x: torch.Tensor, wg8: torch.Tensor, sg: torch.Tensor,
+                      wu8: torch.Tensor, su: torch.Tensor,
+                      bias_gate: Optional[torch.Tensor] = None,
+                      bias_up: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``silu(fp8_linear(x, wg8, sg, bias_gate)) * fp8_linear(x, wu8, su,
+    bias_up)`` in ``x.dtype``; x [..., K], both weights [I, K].
+
+    On a GPU, up to ``FP8_LINEAR_MAX_M`` rows are ONE launch of the fused
+    kernel (csrc/fp8_linear.hip): gate and up pre-activations stay in fp32
+    and never reach memory, and the result is bitwise repeatable and
+    independent of the batch a row sits in. Above it, two ``fp8_linear`` calls
+    (the tiled kernel) and ``swiglu``."""
+    _refuse_grad("fp8_swiglu_linear", x, sg, su, bias_gate, bias_up)
+    ext = dispatch(x)
+    shape = x.shape
+    x2d = x.reshape(-1, shape[-1])
+    if ext is None:
+        g = (x2d.float() @ wg8.float().t()) * sg
+        u = (x2d.float() @ wu8.float().t()) * su
+        if bias_gate is not None:
+            g = g + bias_gate.float()
+        if bias_up is not None:
+            u = u + bias_up.float()
+        out = (g * torch.sigmoid(g) * u).to(x.dtype)
+    elif x2d.shape[0] <= FP8_LINEAR_MAX_M:
+        out = ext.fp8_swiglu_linear(x2d.contiguous(), wg8, sg, wu8, su,
+                                    bias_gate, bias_up)
+    else:
+        out = swiglu(fp8_linear(x2d, wg8, sg, bias_gate),
+                     fp8_linear(x2d, wu8, su, bias_up))
+    return out.view(*shape[:-1], wg8.shape[0])
+
+
+def _keep_fp8_buffers(module: nn.Module, before) -> None:
+    """After an ``_apply`` sweep: a dtype change (.to(bfloat16), .half()) is
+    meant for biases; codes and fp32 scales move device but keep their
+    types. ``before``: name -> buffer as it was."""
+    for name, old in before.items():
+        new = getattr(module, name)
+        if new.dtype != old.dtype:
+            setattr(module, name, old.to(new.device))
+
+
 class Fp8Linear(nn.Module):
     """Linear layer holding e4m3 weight codes and per-channel fp32 scales."""
 
     def __init__(self, w8: torch.Tensor, scale: torch.Tensor,
-                 bias: Optional[torch.Tensor] = None):
+                 bias: Optional[torch.Tensor] = None,
+                 one_launch: bool = False):
         super().__init__()
+        self.one_launch = one_launch
         self.out_features, self.in_features = w8.shape
         self.register_buffer("weight_fp8", w8)
         self.register_buffer("weight_scale", scale)
         self.register_buffer("bias", bias)
 
     @classmethod
-    def from_linear(cls, lin: nn.Linear) -> "Fp8Linear":
+    def from_linear(cls, lin: nn.Linear,
+                    one_launch: bool = False) -> "Fp8Linear":
         w8, scale = quantize_weight_fp8(lin.weight)
         bias = None if lin.bias is None else lin.bias.detach().clone()
-        return cls(w8, scale, bias)
+        return cls(w8, scale, bias, one_launch)
 
     def _apply(self, fn, recurse=True):
-        w8, scale = self.weight_fp8, self.weight_scale
+        before = {n: getattr(self, n) for n in ("weight_fp8", "weight_scale")}
         super()._apply(fn, recurse)
-        # a dtype sweep (.to(bfloat16), .half()) is meant for the bias: the
-        # codes and their fp32 scales move device but keep their types
-        if self.weight_fp8.dtype != w8.dtype:
-            self.weight_fp8 = w8.to(self.weight_fp8.device)
-        if self.weight_scale.dtype != scale.dtype:
-            self.weight_scale = scale.to(self.weight_scale.device)
+        _keep_fp8_buffers(self, before)
         return self
 
     def forward(self, x):
-        return fp8_linear(x, self.weight_fp8, self.weight_scale, self.bias)
+        return fp8_linear(x, self.weight_fp8, self.weight_scale, self.bias,
+                          self.one_launch)
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, "
                 f"out_features={self.out_features}, "
-                f"bias={self.bias is not None}")
+                f"bias={self.bias is not None}"
+                + (", one_launch=True" if self.one_launch else ""))
 
 
-def _swap_linears(parent: nn.Module) -> None:
+class Fp8SwiGLUMLP(nn.Module):
+    """SwiGLU MLP on fp8 weights: gate and up projections and the activation
+    are one fused launch (``fp8_swiglu_linear``), then an ``Fp8Linear`` down
+    projection on the one-launch kernel."""
+
+    _FP8_BUFFERS = ("gate_fp8", "gate_scale", "up_fp8", "up_scale")
+
+    def __init__(self, gate: Fp8Linear, up: Fp8Linear, down: Fp8Linear):
+        super().__init__()
+        assert gate.weight_fp8.shape == up.weight_fp8.shape
+        self.register_buffer("gate_fp8", gate.weight_fp8)
+        self.register_buffer("gate_scale", gate.weight_scale)
+        self.register_buffer("gate_bias", gate.bias)
+        self.register_buffer("up_fp8", up.weight_fp8)
+        self.register_buffer("up_scale", up.weight_scale)
+        self.register_buffer("up_bias", up.bias)
+        self.down_proj = down
+
+    @classmethod
+    def from_mlp(cls, mlp: nn.Module) -> "Fp8SwiGLUMLP":
+        """From any module with gate_proj / up_proj / down_proj linears
+        (``nn.Linear``, ``TunedLinear`` or already ``Fp8Linear``)."""
+        def q(lin):
+            if isinstance(lin, Fp8Linear):
+                return lin
+            return Fp8Linear.from_linear(lin)
+        down = q(mlp.down_proj)
+        down.one_launch = True
+        return cls(q(mlp.gate_proj), q(mlp.up_proj), down)
+
+    def _apply(self, fn, recurse=True):
+        before = {n: getattr(self, n) for n in self._FP8_BUFFERS}
+        super()._apply(fn, recurse)
+        _keep_fp8_buffers(self, before)
+        return self
+
+    def forward(self, x):
+        return self.down_proj(fp8_swiglu_linear(
+            x, self.gate_fp8, self.gate_scale, self.up_fp8, self.up_scale,
+            self.gate_bias, self.up_bias))
+
+
+def _is_swiglu_mlp(mod: nn.Module) -> bool:
+    return all(type(getattr(mod, n, None)) in (nn.Linear, TunedLinear,
+                                               Fp8Linear)
+               for n in ("gate_proj", "up_proj", "down_proj"))
+
+
+def _swap_linears(parent: nn.Module, one_launch: bool = False) -> None:
     for name, child in parent.named_children():
         if type(child) in (nn.Linear, TunedLinear):
-            setattr(parent, name, Fp8Linear.from_linear(child))
-        elif isinstance(child, Fp8Linear):
+            setattr(parent, name, Fp8Linear.from_linear(child, one_launch))
+        elif one_launch and name == "mlp" and _is_swiglu_mlp(child):
+            setattr(parent, name, Fp8SwiGLUMLP.from_mlp(child))
+        elif isinstance(child, (Fp8Linear, Fp8SwiGLUMLP)):
             continue
         elif hasattr(child, "tp") and hasattr(child, "group") \
                 and hasattr(child, "weight"):
@@ -139,20 +249,26 @@ def _swap_linears(parent: nn.Module) -> None:
                 "fp8 weights for TP layers are not supported. Quantise the "
                 "unsharded model (and serve it on one device) instead.")
         else:
-            _swap_linears(child)
+            _swap_linears(child, one_launch)
 
 
-def quantize_model_fp8(model: nn.Module, include_lm_head: bool = False):
+def quantize_model_fp8(model: nn.Module, include_lm_head: bool = False,
+                       one_launch: bool = False):
     """Swap, in place, every ``nn.Linear`` / ``TunedLinear`` inside
     ``model.layers`` for an ``Fp8Linear``; with ``include_lm_head`` also
     ``model.lm_head`` (a tied head gets its own fp8 copy; the embedding table
-    is left as it is). Returns the model."""
+    is left as it is). Returns the model.
+
+    ``one_launch``: every ``Fp8Linear`` created takes the one-launch kernel at
+    decode-sized batches, and each ``mlp`` child made of gate_proj / up_proj /
+    down_proj linears becomes an ``Fp8SwiGLUMLP`` (fused gate/up/activation).
+    """
     if getattr(model, "_tp_group", None) is not None:
         raise NotImplementedError(
             "quantize_model_fp8: the model is tensor-parallel sharded; fp8 "
             "weights for TP layers are not supported. Quantise the "
             "unsharded model instead.")
-    _swap_linears(model.layers)
+    _swap_linears(model.layers, one_launch)
     if not any(isinstance(m, Fp8Linear) for m in model.layers.modules()):
         raise ValueError("quantize_model_fp8: no linear layer found under "
                          "model.layers")
@@ -162,5 +278,5 @@ def quantize_model_fp8(model: nn.Module, include_lm_head: bool = False):
             raise NotImplementedError(
                 f"quantize_model_fp8: lm_head is a {type(head).__name__}, "
                 "expected an unsharded nn.Linear")
-        model.lm_head = Fp8Linear.from_linear(head)
+        model.lm_head = Fp8Linear.from_linear(head, one_launch)
     return model
