@@ -34,6 +34,9 @@ __global__ void ce_fwd_kernel(const short* __restrict__ logits,
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float x = vals[j];
+        // masked (-inf) logits and the ragged tail add nothing, and with
+        // m still -inf exp(x - m) would be NaN
+        if (x == -INFINITY) continue;
         if (x > m) {
           s *= __expf(m - x);
           m = x;
@@ -130,6 +133,9 @@ std::vector<torch::Tensor> cross_entropy_forward(torch::Tensor logits,
               "cross_entropy: bf16 logits only on GPU");
   TORCH_CHECK(target.scalar_type() == torch::kLong);
   const int rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(logits.is_contiguous() && target.is_cuda() &&
+                  target.is_contiguous() && target.numel() == rows,
+              "cross_entropy: target must be a contiguous GPU tensor [rows]");
   auto lse = torch::empty({rows}, logits.options().dtype(torch::kFloat32));
   auto loss = torch::zeros({}, logits.options().dtype(torch::kFloat32));
   auto nvalid = torch::zeros({}, logits.options().dtype(torch::kInt32));

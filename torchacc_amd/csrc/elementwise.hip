@@ -269,7 +269,10 @@ __global__ void add_rmsnorm_fwd_kernel(const short* __restrict__ x,
         for (int j = 0; j < 8; ++j) {
           float f = AttnElem<FP16>::to_f32(v[j]) + AttnElem<FP16>::to_f32(rv[j]);
           o[j] = AttnElem<FP16>::from_f32(f);
-          ss += f * f;
+          // inv_rms belongs to the ROUNDED sum: that is what the second
+          // pass normalises and what backward gets as r_saved
+          float fr = AttnElem<FP16>::to_f32(o[j]);
+          ss += fr * fr;
         }
       } else {
 #pragma unroll
@@ -546,11 +549,22 @@ static inline int grid_for(long work, int block) {
   return (int)std::min<long>(g, 2048);
 }
 
+// The norm kernels read w as H contiguous elements of x's dtype: a weight
+// kept in another dtype (fp32 under autocast) is cast here; dw goes back in
+// the weight's own dtype.
+static inline torch::Tensor norm_weight(const torch::Tensor& w,
+                                        const torch::Tensor& x, int H) {
+  TORCH_CHECK(w.is_cuda() && w.numel() == H,
+              "rmsnorm: weight must be a GPU tensor with hidden-size elements");
+  return w.to(x.scalar_type()).contiguous();
+}
+
 std::vector<torch::Tensor> rmsnorm_forward(torch::Tensor x, torch::Tensor w,
                                            double eps) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous());
   const int H = x.size(-1);
   const long rows = x.numel() / H;
+  w = norm_weight(w, x, H);
   auto y = torch::empty_like(x);
   auto inv_rms = torch::empty({rows}, x.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStream();
@@ -588,6 +602,17 @@ std::vector<torch::Tensor> rmsnorm_backward(torch::Tensor dy, torch::Tensor x,
   const bool f16 = x.scalar_type() == torch::kHalf;
   const int H = x.size(-1);
   const long rows = x.numel() / H;
+  TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
+  TORCH_CHECK(x.is_contiguous() && dy.is_cuda() && dy.is_contiguous() &&
+                  dy.scalar_type() == x.scalar_type() &&
+                  dy.sizes() == x.sizes(),
+              "rmsnorm backward: dy must match x");
+  TORCH_CHECK(inv_rms.is_cuda() && inv_rms.is_contiguous() &&
+                  inv_rms.scalar_type() == torch::kFloat32 &&
+                  inv_rms.numel() == rows,
+              "rmsnorm backward: inv_rms must be fp32 [rows]");
+  const auto w_dtype = w.scalar_type();
+  w = norm_weight(w, x, H);
   auto dx = torch::empty_like(x);
   auto dw32 = torch::zeros({H}, x.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStream();
@@ -602,7 +627,7 @@ std::vector<torch::Tensor> rmsnorm_backward(torch::Tensor dy, torch::Tensor x,
                          inv_rms.data_ptr<float>(), (short*)dx.data_ptr(),
                          dw32.data_ptr<float>(), (int)rows, H));
   HIP_CHECK_LAST();
-  return {dx, dw32.to(w.scalar_type())};
+  return {dx, dw32.to(w_dtype)};
 }
 
 std::vector<torch::Tensor> rope_forward(torch::Tensor q, torch::Tensor k,
@@ -655,6 +680,10 @@ torch::Tensor swiglu_forward(torch::Tensor g, torch::Tensor u) {
               "swiglu: bf16/fp16 only on GPU");
   const bool f16 = g.scalar_type() == torch::kHalf;
   TORCH_CHECK(g.numel() % 8 == 0);
+  TORCH_CHECK(g.is_contiguous() && u.is_cuda() && u.is_contiguous() &&
+                  u.scalar_type() == g.scalar_type() &&
+                  u.sizes() == g.sizes(),
+              "swiglu: up must match gate");
   auto y = torch::empty_like(g);
   auto stream = at::hip::getCurrentHIPStream();
   const long n8 = g.numel() / 8;
@@ -683,6 +712,15 @@ std::vector<torch::Tensor> swiglu_backward(torch::Tensor dy, torch::Tensor g,
   TORCH_CHECK(g.is_cuda() && (g.scalar_type() == torch::kBFloat16 ||
                               g.scalar_type() == torch::kHalf));
   const bool f16 = g.scalar_type() == torch::kHalf;
+  TORCH_CHECK(g.numel() % 8 == 0);
+  TORCH_CHECK(g.is_contiguous() && u.is_cuda() && u.is_contiguous() &&
+                  u.scalar_type() == g.scalar_type() &&
+                  u.sizes() == g.sizes(),
+              "swiglu backward: up must match gate");
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
+                  dy.scalar_type() == g.scalar_type() &&
+                  dy.sizes() == g.sizes(),
+              "swiglu backward: dy must match gate");
   auto dg = torch::empty_like(g);
   auto du = torch::empty_like(u);
   auto stream = at::hip::getCurrentHIPStream();
@@ -721,9 +759,15 @@ std::vector<torch::Tensor> add_rmsnorm_forward(torch::Tensor x,
               "add_rmsnorm: bf16/fp16 only on GPU");
   const bool f16 = x.scalar_type() == torch::kHalf;
   const int H = x.size(-1);
-  TORCH_CHECK(H % 8 == 0);
+  TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
   const long rows = x.numel() / H;
   const bool has_resid = resid.numel() > 0;
+  TORCH_CHECK(!has_resid ||
+                  (resid.is_cuda() && resid.is_contiguous() &&
+                   resid.scalar_type() == x.scalar_type() &&
+                   resid.sizes() == x.sizes()),
+              "add_rmsnorm: residual must match x");
+  w = norm_weight(w, x, H);
   auto y = torch::empty_like(x);
   auto resid_out = torch::empty_like(x);
   auto inv_rms = torch::empty({rows}, x.options().dtype(torch::kFloat32));
@@ -762,9 +806,29 @@ std::vector<torch::Tensor> add_rmsnorm_backward(torch::Tensor dy,
                                                 torch::Tensor r_saved,
                                                 torch::Tensor w,
                                                 torch::Tensor inv_rms) {
+  TORCH_CHECK(r_saved.is_cuda() && r_saved.is_contiguous() &&
+                  (r_saved.scalar_type() == torch::kBFloat16 ||
+                   r_saved.scalar_type() == torch::kHalf),
+              "add_rmsnorm backward: bf16/fp16 only on GPU");
   const int H = r_saved.size(-1);
+  TORCH_CHECK(H % 8 == 0, "hidden size must be a multiple of 8");
   const long rows = r_saved.numel() / H;
   const bool has_dresid = dresid.numel() > 0;
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
+                  dy.scalar_type() == r_saved.scalar_type() &&
+                  dy.sizes() == r_saved.sizes(),
+              "add_rmsnorm backward: dy must match the saved residual");
+  TORCH_CHECK(!has_dresid ||
+                  (dresid.is_cuda() && dresid.is_contiguous() &&
+                   dresid.scalar_type() == r_saved.scalar_type() &&
+                   dresid.sizes() == r_saved.sizes()),
+              "add_rmsnorm backward: dresid must match the saved residual");
+  TORCH_CHECK(inv_rms.is_cuda() && inv_rms.is_contiguous() &&
+                  inv_rms.scalar_type() == torch::kFloat32 &&
+                  inv_rms.numel() == rows,
+              "add_rmsnorm backward: inv_rms must be fp32 [rows]");
+  const auto w_dtype = w.scalar_type();
+  w = norm_weight(w, r_saved, H);
   auto dx = torch::empty_like(r_saved);
   auto dw32 = torch::zeros({H}, r_saved.options().dtype(torch::kFloat32));
   auto stream = at::hip::getCurrentHIPStream();
@@ -801,5 +865,5 @@ std::vector<torch::Tensor> add_rmsnorm_backward(torch::Tensor dy,
                            (int)rows, H, has_dresid);
       });
   HIP_CHECK_LAST();
-  return {dx, dw32.to(w.scalar_type())};
+  return {dx, dw32.to(w_dtype)};
 }
