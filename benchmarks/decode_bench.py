@@ -32,11 +32,13 @@ def main():
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="run the prompt in pieces of at most this many "
                         "tokens (eager path)")
-    p.add_argument("--weight-dtype", default=None, choices=["fp8"],
+    p.add_argument("--weight-dtype", default=None, choices=["fp8", "mxfp4"],
                    help="quantise the decoder projections to e4m3 weights "
-                        "(quantize_model_fp8; default: 16-bit weights)")
+                        "(quantize_model_fp8) or to MXFP4 ones "
+                        "(quantize_model_mxfp4; default: 16-bit weights)")
     p.add_argument("--fp8-lm-head", action="store_true",
-                   help="with --weight-dtype fp8: quantise lm_head too")
+                   help="with --weight-dtype fp8 or mxfp4: quantise lm_head "
+                        "too")
     p.add_argument("--fp8-one-launch", action="store_true",
                    help="with --weight-dtype fp8: one-launch projections and "
                         "the fused gate/up SwiGLU MLP (one_launch=True)")
@@ -65,6 +67,13 @@ def main():
         from torchacc_amd.ops import quantize_model_fp8
         quantize_model_fp8(model, include_lm_head=args.fp8_lm_head,
                            one_launch=args.fp8_one_launch)
+    elif args.weight_dtype == "mxfp4":
+        from torchacc_amd.ops import quantize_model_mxfp4
+        quantize_model_mxfp4(model, include_lm_head=args.fp8_lm_head)
+    # bytes of the parameters and buffers under the layers and the head
+    weight_bytes = sum(t.numel() * t.element_size() for mod in
+                       (model.layers, model.lm_head)
+                       for t in list(mod.parameters()) + list(mod.buffers()))
     ids = torch.randint(0, mcfg.vocab_size, (args.batch, args.prompt),
                         device=dev)
 
@@ -90,7 +99,8 @@ def main():
     extra = {}
     if args.weight_dtype is not None:
         extra = {"weight_dtype": args.weight_dtype,
-                 "fp8_lm_head": args.fp8_lm_head}
+                 "fp8_lm_head": args.fp8_lm_head,
+                 "weight_bytes": weight_bytes}
         if args.fp8_one_launch:
             extra["fp8_one_launch"] = True
     print(json.dumps({

@@ -30,6 +30,7 @@ sources = [
         "flash_attn_extra_bwd.hip",
         "gemm.hip",
         "fp8_linear.hip",
+        "mxfp4_linear.hip",
     )
 ]
 

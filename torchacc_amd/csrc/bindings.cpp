@@ -141,6 +141,23 @@ torch::Tensor fp8_swiglu_linear(torch::Tensor x, torch::Tensor wg8,
 std::vector<long> fp8_wide_instance(long n, long k, long num_cus,
                                     bool swiglu);
 
+// mxfp4_linear.hip; waves / tiles: 0 = mxfp4_linear_instance's pick
+torch::Tensor mxfp4_linear(torch::Tensor x, torch::Tensor codes,
+                           torch::Tensor scales,
+                           c10::optional<torch::Tensor> bias, long waves,
+                           long tiles);
+torch::Tensor mxfp4_swiglu_linear(torch::Tensor x, torch::Tensor gate_codes,
+                                  torch::Tensor gate_scales,
+                                  torch::Tensor up_codes,
+                                  torch::Tensor up_scales,
+                                  c10::optional<torch::Tensor> bias_gate,
+                                  c10::optional<torch::Tensor> bias_up,
+                                  long waves, long tiles);
+torch::Tensor mxfp4_dequantize(torch::Tensor codes, torch::Tensor scales,
+                               torch::ScalarType dtype);
+std::vector<long> mxfp4_linear_instance(long n, long k, long num_cus,
+                                        bool swiglu);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torchacc_amd CDNA4 (gfx950) kernels";
   m.def("rmsnorm_forward", &rmsnorm_forward);
@@ -189,4 +206,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("bias_up") = pybind11::none(),
         pybind11::arg("waves") = 0);
   m.def("fp8_wide_instance", &fp8_wide_instance);
+  m.def("mxfp4_linear", &mxfp4_linear, pybind11::arg("x"),
+        pybind11::arg("codes"), pybind11::arg("scales"),
+        pybind11::arg("bias") = pybind11::none(), pybind11::arg("waves") = 0,
+        pybind11::arg("tiles") = 0);
+  m.def("mxfp4_swiglu_linear", &mxfp4_swiglu_linear, pybind11::arg("x"),
+        pybind11::arg("gate_codes"), pybind11::arg("gate_scales"),
+        pybind11::arg("up_codes"), pybind11::arg("up_scales"),
+        pybind11::arg("bias_gate") = pybind11::none(),
+        pybind11::arg("bias_up") = pybind11::none(),
+        pybind11::arg("waves") = 0, pybind11::arg("tiles") = 0);
+  m.def("mxfp4_dequantize", &mxfp4_dequantize);
+  m.def("mxfp4_linear_instance", &mxfp4_linear_instance);
 }

@@ -1,0 +1,532 @@
+// Weight-only MXFP4 linear layer for decode-sized batches (W4A16):
+//   y[M,N] = x[M,K] @ dequant(W4[N,K])^T (+ bias[N])
+// x, y bf16 or fp16, fp32 accumulation. The weight is in the OCP microscaling
+// format: e2m1 elements (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), two per byte (element
+// 2i in bits 0..3 of byte i, 2i+1 in bits 4..7), codes [N, K/2] row-major, and
+// one e8m0 scale byte per 32 elements along K, scales [N, K/32]: group g of row
+// n is multiplied by 2^(scales[n,g] - 127). A quarter of the 16-bit bytes and
+// half of the e4m3 ones that fp8_linear.hip streams.
+//
+// Matrix instruction and operand order as in fp8_linear.hip:
+// v_mfma_f32_16x16x32_{bf16,f16} with the WEIGHTS as the A operand (lane l
+// holds channel l&15, k-slots 8*(l>>4)..+7), up to 16 activation rows as the B
+// operand, so the result is y^T: lane l owns activation row l&15 and channels
+// 4*(l>>4)..+3 of a tile, an 8-byte store along N.
+//
+// Weight stream: a lane's 16-byte load is 32 codes of its row, which is exactly
+// one scale group. The four lane groups of a row cover 64 contiguous bytes, and
+// a wave step issues the two loads of a 128-byte line back to back: 256 codes
+// per row and step. Dword s of the load feeds MFMA K-step s (4 per load)
+// through v_cvt_scalef32_pk_{bf16,f16}_fp4, one instruction per byte (two
+// elements) with the group's scale applied: 16 converts per load. The product
+// element * 2^e is exact in the 16-bit type (see the range note below), so the
+// conversion rounds nothing. The reduction order inside K is free, so the x
+// fragment follows the same permutation: lane (j, g) reads
+// x[j][k0 + 32g + 8s .. +7] for K-step s, 64 contiguous bytes per load.
+//
+// Group scales: the 8 scale bytes of a row's step are contiguous
+// (scales[row][8t .. 8t+7]); a lane fetches them with one 8-byte load (rows
+// start at any byte when K/32 is no multiple of 8, so the load is declared
+// unaligned) and selects byte 4h + g for half h. The f32 scale is
+// bitcast(max(e, 1) << 23): e = 0 would be 2^-127, an fp32 subnormal, and is
+// CLAMPED to 2^-126. The quantiser never produces byte 0, and 255 (NaN) is
+// rejected there.
+//
+// Exactness range: element * 2^e is a bf16 value for every scale byte 1..252
+// (exponents -126..125; results below 2^-126 are bf16 subnormals). In fp16 it
+// holds for exponents -14..12 (bytes 113..139) only; the fp16 contract is
+// limited to that range.
+//
+// One launch for every (N, K): K is cut only across the W in {4, 8} waves of a
+// workgroup, in contiguous, balanced runs of steps; the W accumulators are
+// summed through LDS in wave order after one barrier (the fp8_wide_kernel
+// pattern). No partials, no combine, no atomics: the result is bitwise
+// repeatable, and since W, NT and every K boundary come from (N, K, CU count)
+// alone, a row's bits depend neither on the batch it sits in nor on its
+// position.
+//
+// Tiles per wave: against the fp8 kernel the weight bytes per MFMA halve while
+// the x bytes stay, so a wave owns NT in {1, 2, 4} channel tiles per x
+// fragment (an A fragment costs 4 VGPRs per 32 codes). The x fragments of one
+// half (MT x 4 x 16 bytes) are loaded per half, not per step, which keeps
+// MT = 4 at 64 VGPRs of x. Built instances (W, NT): (4,1) (8,1) (4,2) (8,2)
+// (4,4); (8,4) would need 128 KiB of reduction LDS at MT = 4 and is left out.
+//
+// Epilogues: PLAIN y = acc (+ bias). SWIGLU: the wave's NT tiles are NT/2
+// tiles of the GATE weight and the same NT/2 tiles of the UP weight (two code
+// pointers, two scale pointers, nothing re-laid); one x fragment feeds both,
+// y = silu(g (+ bg)) * (u (+ bu)) in fp32; g and u never reach memory.
+//
+// Tails: channels >= N read a clamped row and are predicated at the store;
+// N % 4 != 0 takes scalar stores; rows >= M read row M-1 and are never stored;
+// the one ragged step at the end of K (K % 256 != 0, whole 32-code groups)
+// contributes zeros and reads its scale bytes one by one, predicated.
+//
+// mxfp4_dequantize further down writes the [N, K] 16-bit weight with the same
+// convert (16-byte loads and stores); it serves M > 64 and checkpoint export.
+#include <torch/extension.h>
+#include <ATen/hip/HIPContext.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+#include "attn_common.h"
+
+// packed fp32 VALU forms are kept out of this file's device code
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
+                             apply_to = function)
+
+namespace {
+
+constexpr int MX4_STEP = 256;        // codes per wave step: one 128-byte line/row
+constexpr int MX4_GROUP = 32;        // codes per scale byte
+constexpr long MX4_MAX_M = 64;
+
+typedef __bf16 mx4_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 mx4_bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 mx4_f16x2 __attribute__((ext_vector_type(2)));
+// the 8 scale bytes of a row's step; rows start at any byte
+typedef unsigned mx4_u32x2_u __attribute__((ext_vector_type(2), aligned(1)));
+
+// f32 2^(e - 127) from an e8m0 byte; e = 0 (an fp32 subnormal) clamps to 2^-126
+DEVINLINE float mx4_scale(unsigned e) {
+  return __builtin_bit_cast(float, max(e, 1u) << 23);
+}
+
+// 8 e2m1 codes (one dword) times the group scale -> one 16-bit x8 A fragment;
+// byte i holds elements 2i (low nibble) and 2i+1
+template <bool FP16>
+DEVINLINE attn_u32x4 mx4_cvt8(unsigned c, float sc) {
+  attn_u32x4 a;
+  if constexpr (FP16) {
+    a[0] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(c, sc, 0));
+    a[1] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(c, sc, 1));
+    a[2] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(c, sc, 2));
+    a[3] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(c, sc, 3));
+  } else {
+    a[0] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 0));
+    a[1] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 1));
+    a[2] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 2));
+    a[3] = __builtin_bit_cast(
+        unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3));
+  }
+  return a;
+}
+
+template <bool FP16>
+DEVINLINE f32x4 mx4_mfma(attn_u32x4 a, attn_u32x4 b, f32x4 c) {
+  if constexpr (FP16) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(
+        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
+        c, 0, 0, 0);
+  } else {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+        __builtin_bit_cast(mx4_bf16x8, a), __builtin_bit_cast(mx4_bf16x8, b),
+        c, 0, 0, 0);
+  }
+}
+
+// One 256-code step t of a wave. Lane (j, g), half h: codes
+// [256t + 128h + 32g, +32) of its row of every tile, i.e. 16 bytes at
+// 128t + 64h + 16g, and scale byte 8t + 4h + g. Both halves' codes and the
+// step's scale bytes are requested first; per half the lane then loads its 32
+// activations of every column block and runs 4 K-steps x NT x MT MFMAs.
+// TAIL is the one ragged step at the end of K (K % 256 != 0): groups at or
+// past K contribute zeros (codes and activations both zeroed).
+template <bool FP16, int MT, bool TAIL, int NT>
+DEVINLINE void mx4_step(const unsigned char* const (&wrow)[NT],
+                        const unsigned char* const (&srow)[NT],
+                        const short* const (&xrow)[MT], int t, int g, int K,
+                        f32x4 (&acc)[NT][MT]) {
+  attn_u32x4 wv[2][NT];
+  float sc[2][NT];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = t * MX4_STEP + h * 128 + g * MX4_GROUP;
+    const bool live = !TAIL || k < K;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      wv[h][nt] = attn_u32x4{0u, 0u, 0u, 0u};
+      if (live)
+        wv[h][nt] = *reinterpret_cast<const attn_u32x4*>(wrow[nt] + (k >> 1));
+    }
+  }
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    if constexpr (TAIL) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int gi = t * 8 + h * 4 + g;
+        sc[h][nt] = mx4_scale(gi * MX4_GROUP < K ? srow[nt][gi] : 127u);
+      }
+    } else {
+      const mx4_u32x2_u sv =
+          *reinterpret_cast<const mx4_u32x2_u*>(srow[nt] + t * 8);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        sc[h][nt] = mx4_scale((sv[h] >> (8 * g)) & 0xFFu);
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int k = t * MX4_STEP + h * 128 + g * MX4_GROUP;
+    const bool live = !TAIL || k < K;
+    attn_u32x4 xv[MT][4];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        xv[mt][s] = attn_u32x4{0u, 0u, 0u, 0u};
+        if (live)
+          xv[mt][s] =
+              *reinterpret_cast<const attn_u32x4*>(xrow[mt] + k + 8 * s);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const attn_u32x4 a = mx4_cvt8<FP16>(wv[h][nt][s], sc[h][nt]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          acc[nt][mt] = mx4_mfma<FP16>(a, xv[mt][s], acc[nt][mt]);
+      }
+    }
+  }
+}
+
+// Bias, convert and store channels n..n+3 (n % 4 == 0) of row m. SWIGLU:
+// silu(v (+ b0)) * (u (+ b1)) in fp32.
+template <bool FP16, bool SWIGLU>
+DEVINLINE void mx4_finish4(f32x4 v, f32x4 u, long m, int n, int N,
+                           const short* __restrict__ b0,
+                           const short* __restrict__ b1,
+                           short* __restrict__ y) {
+  const bool vec = (N & 3) == 0;  // then n + 3 < N, 8-byte aligned row start
+  s16x4 ov;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int c = vec ? n + r : min(n + r, N - 1);
+    float o = v[r];
+    if (b0 != nullptr) o += AttnElem<FP16>::to_f32(b0[c]);
+    if constexpr (SWIGLU) {
+      float up = u[r];
+      if (b1 != nullptr) up += AttnElem<FP16>::to_f32(b1[c]);
+      // exp overflows to +inf for o < -88: the quotient is then -0, silu's
+      // limit
+      o = o / (1.f + __expf(-o)) * up;
+    }
+    ov[r] = AttnElem<FP16>::from_f32(o);
+  }
+  if (vec) {
+    *reinterpret_cast<s16x4*>(y + m * N + n) = ov;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (n + r < N) y[m * N + n + r] = ov[r];
+  }
+}
+
+// grid = ceil(N / BN), BN = 16 * NT (PLAIN) or 8 * NT (SWIGLU); block = W * 64.
+// PLAIN reads (w0, s0, b0) only. LDS: red[W][NT * MT][64] f32x4, at most 64 KiB.
+template <bool FP16, int MT, int W, int NT, bool SWIGLU>
+__global__ __launch_bounds__(W * WAVE)
+void mxfp4_linear_kernel(const short* __restrict__ x,
+                         const unsigned char* __restrict__ w0,
+                         const unsigned char* __restrict__ w1,
+                         const unsigned char* __restrict__ s0,
+                         const unsigned char* __restrict__ s1,
+                         const short* __restrict__ b0,
+                         const short* __restrict__ b1,
+                         short* __restrict__ y, int M, int N, int K) {
+  static_assert(!SWIGLU || NT % 2 == 0, "SWIGLU: as many gate as up tiles");
+  static_assert(W * NT * MT * WAVE * sizeof(f32x4) <= 64 * 1024, "LDS");
+  constexpr int CT = SWIGLU ? NT / 2 : NT;   // channel tiles per workgroup
+  constexpr int BN = 16 * CT;
+  __shared__ f32x4 red[W][NT * MT][WAVE];
+  const int tid = threadIdx.x, lane = tid % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int j = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * BN;
+
+  // contiguous, balanced runs of steps over the W waves
+  const int T = (K + MX4_STEP - 1) / MX4_STEP, Tfull = K / MX4_STEP;
+  const int t0 = (int)((long)wave * T / W);
+  const int t1 = (int)((long)(wave + 1) * T / W);
+
+  // tiles 0..CT-1 are w0's; SWIGLU: tiles CT..NT-1 are the same channels of w1.
+  // Rows past the end are clamped: loaded, multiplied, never stored.
+  const unsigned char* wrow[NT];
+  const unsigned char* srow[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const long row = min(n0 + (nt % CT) * 16 + j, N - 1);
+    wrow[nt] = (nt < CT ? w0 : w1) + row * (K / 2);
+    srow[nt] = (nt < CT ? s0 : s1) + row * (K / MX4_GROUP);
+  }
+  const short* xrow[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+    xrow[mt] = x + (long)min(mt * 16 + j, M - 1) * K;
+
+  f32x4 acc[NT][MT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int tm = min(t1, Tfull);
+  for (int t = t0; t < tm; ++t)
+    mx4_step<FP16, MT, false>(wrow, srow, xrow, t, g, K, acc);
+  if (t1 > Tfull)  // only the last wave, only when K % 256 != 0
+    mx4_step<FP16, MT, true>(wrow, srow, xrow, Tfull, g, K, acc);
+
+#pragma unroll
+  for (int i = 0; i < NT * MT; ++i) red[wave][i][lane] = acc[i / MT][i % MT];
+  __syncthreads();
+  // item (channel tile ct, column block mt, lane l) sums slot ct * MT + mt of
+  // waves 0..W-1 in that order; SWIGLU also the up slot (CT + ct) * MT + mt
+  constexpr int ITEMS = CT * MT * WAVE;
+  for (int idx = tid; idx < ITEMS; idx += W * WAVE) {
+    const int i = idx / WAVE, l = idx % WAVE;
+    const int m = (i % MT) * 16 + (l & 15);
+    const int n = n0 + (i / MT) * 16 + 4 * (l >> 4);
+    if (m >= M || n >= N) continue;
+    f32x4 v = red[0][i][l];
+#pragma unroll
+    for (int wv = 1; wv < W; ++wv) v += red[wv][i][l];
+    f32x4 u = v;
+    if constexpr (SWIGLU) {
+      u = red[0][CT * MT + i][l];
+#pragma unroll
+      for (int wv = 1; wv < W; ++wv) u += red[wv][CT * MT + i][l];
+    }
+    mx4_finish4<FP16, SWIGLU>(v, u, m, n, N, b0, b1, y);
+  }
+}
+
+// A thread converts one scale group: 16 bytes of codes in, 64 bytes out.
+template <bool FP16>
+__global__ __launch_bounds__(256)
+void mxfp4_dequantize_kernel(const unsigned char* __restrict__ codes,
+                             const unsigned char* __restrict__ scales,
+                             short* __restrict__ out, long groups) {
+  const long gi = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= groups) return;
+  const attn_u32x4 c = *reinterpret_cast<const attn_u32x4*>(codes + gi * 16);
+  const float sc = mx4_scale(scales[gi]);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    *reinterpret_cast<attn_u32x4*>(out + gi * MX4_GROUP + 8 * s) =
+        mx4_cvt8<FP16>(c[s], sc);
+}
+
+}  // namespace
+
+#pragma clang attribute pop
+
+// The (W, NT) instance for an [N, K] weight (SWIGLU: N = I, a gate/up pair,
+// NT counts gate and up tiles together) on a device with num_cus compute
+// units. A function of (N, K, num_cus) only, never of M. PLAIN takes the
+// widest tile count that still gives every CU a workgroup, since one x
+// fragment then feeds the most weight bytes; below that, one channel tile on 8
+// waves (which needs 8 steps in K, so that every wave keeps a whole one).
+// SWIGLU takes four tiles only from two workgroups per CU on: at 1.3 per CU
+// (I = 11008 on 256 CUs) the second, partial round of workgroups cost more at
+// M <= 16 than the shared x fragment saved (profiles/r19_mxfp4_linear.md).
+std::vector<long> mxfp4_linear_instance(long n, long k, long num_cus,
+                                        bool swiglu) {
+  const long steps = (k + MX4_STEP - 1) / MX4_STEP;
+  const long w8 = steps >= 8 ? 8 : 4;
+  const long wg16 = (n + 15) / 16, wg32 = (n + 31) / 32, wg64 = (n + 63) / 64;
+  if (swiglu) {
+    if (wg32 >= 2 * num_cus) return {4, 4};
+    return {wg16 >= 2 * num_cus ? 4 : w8, 2};
+  }
+  if (wg64 >= num_cus) return {4, 4};
+  if (wg32 >= num_cus) return {4, 2};
+  return {w8, 1};
+}
+
+namespace {
+
+// one (codes, scales, bias) triple of a call against x [M, K]
+void mx4_check(const char* op, const torch::Tensor& x,
+               const torch::Tensor& codes, const torch::Tensor& scales,
+               const c10::optional<torch::Tensor>& bias) {
+  TORCH_CHECK(codes.is_cuda() && scales.is_cuda() &&
+                  codes.device() == x.device() &&
+                  scales.device() == x.device(),
+              op, ": codes and scales on x's GPU required");
+  TORCH_CHECK(codes.dim() == 2 && scales.dim() == 2 &&
+                  codes.scalar_type() == torch::kByte &&
+                  scales.scalar_type() == torch::kByte,
+              op, ": codes [N,K/2] uint8, scales [N,K/32] uint8");
+  const long K = x.size(1);
+  TORCH_CHECK(codes.is_contiguous() && scales.is_contiguous() &&
+                  codes.size(1) * 2 == K && scales.size(1) * MX4_GROUP == K &&
+                  scales.size(0) == codes.size(0),
+              op, ": contiguous operands of matching shape");
+  TORCH_CHECK((uintptr_t)codes.data_ptr() % 16 == 0,
+              op, ": codes must be 16-byte aligned");
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                    bias->scalar_type() == x.scalar_type() &&
+                    bias->dim() == 1 && bias->size(0) == codes.size(0) &&
+                    bias->is_contiguous() &&
+                    (uintptr_t)bias->data_ptr() % 8 == 0,
+                op, ": bias must be [N], contiguous, aligned, x's dtype");
+  }
+}
+
+// Shared front end: PLAIN when c1 is absent, SWIGLU otherwise.
+torch::Tensor mx4_launch(const char* op, torch::Tensor x, torch::Tensor c0,
+                         torch::Tensor s0, c10::optional<torch::Tensor> b0,
+                         const torch::Tensor* c1, const torch::Tensor* s1,
+                         c10::optional<torch::Tensor> b1, long waves,
+                         long tiles) {
+  const bool swiglu = c1 != nullptr;
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+                  (uintptr_t)x.data_ptr() % 16 == 0,
+              op, ": x must be a contiguous, aligned [M,K] GPU tensor");
+  const bool fp16 = x.scalar_type() == torch::kHalf;
+  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
+              op, ": x must be bf16 or fp16");
+  const long M = x.size(0), K = x.size(1);
+  TORCH_CHECK(K >= MX4_GROUP && K % MX4_GROUP == 0,
+              op, ": K must be a positive multiple of 32");
+  mx4_check(op, x, c0, s0, b0);
+  if (swiglu) {
+    mx4_check(op, x, *c1, *s1, b1);
+    TORCH_CHECK(c1->size(0) == c0.size(0), op, ": gate/up shape mismatch");
+  }
+  const long N = c0.size(0);
+  TORCH_CHECK(M >= 1 && M <= MX4_MAX_M, op, ": 1 <= M <= 64");
+  TORCH_CHECK(N >= 1 && 64 * K < (1L << 31) && 128 * N < (1L << 31),
+              op, ": problem too large");
+
+  const auto inst = mxfp4_linear_instance(
+      N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
+      swiglu);
+  const long W = waves > 0 ? waves : inst[0];
+  const long NT = tiles > 0 ? tiles : inst[1];
+  TORCH_CHECK((W == 4 || W == 8) && (NT == 1 || NT == 2 || NT == 4) &&
+                  !(W == 8 && NT == 4) && !(swiglu && NT == 1),
+              op, ": instances are (waves, tiles) in (4,1) (8,1) (4,2) (8,2) "
+                  "(4,4); SWIGLU counts gate and up tiles, so 2 or 4");
+
+  auto y = torch::empty({M, N}, x.options());
+  auto stream = at::hip::getCurrentHIPStream();
+  const long bn = swiglu ? 8 * NT : 16 * NT;
+  const dim3 grid((unsigned)((N + bn - 1) / bn)), block((unsigned)(W * WAVE));
+  const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
+  auto bp = [](const c10::optional<torch::Tensor>& b) {
+    return b.has_value() ? (const short*)b->data_ptr() : nullptr;
+  };
+#define MX4_LAUNCH(MTV, WV, NTV, SW)                                          \
+  hipLaunchKernelGGL((mxfp4_linear_kernel<kFP16, MTV, WV, NTV, SW>), grid,    \
+                     block, 0, stream, (const short*)x.data_ptr(),            \
+                     (const unsigned char*)c0.data_ptr(),                     \
+                     SW ? (const unsigned char*)c1->data_ptr() : nullptr,     \
+                     (const unsigned char*)s0.data_ptr(),                     \
+                     SW ? (const unsigned char*)s1->data_ptr() : nullptr,     \
+                     bp(b0), bp(b1), (short*)y.data_ptr(), (int)M, (int)N,    \
+                     (int)K)
+#define MX4_INSTANCE(MTV)                                   \
+  do {                                                      \
+    if (swiglu) {                                           \
+      if (NT == 4) MX4_LAUNCH(MTV, 4, 4, true);             \
+      else if (W == 4) MX4_LAUNCH(MTV, 4, 2, true);         \
+      else MX4_LAUNCH(MTV, 8, 2, true);                     \
+    } else if (NT == 4) {                                   \
+      MX4_LAUNCH(MTV, 4, 4, false);                         \
+    } else if (NT == 2) {                                   \
+      if (W == 4) MX4_LAUNCH(MTV, 4, 2, false);             \
+      else MX4_LAUNCH(MTV, 8, 2, false);                    \
+    } else {                                                \
+      if (W == 4) MX4_LAUNCH(MTV, 4, 1, false);             \
+      else MX4_LAUNCH(MTV, 8, 1, false);                    \
+    }                                                       \
+  } while (0)
+  FP16_SWITCH(fp16, {
+    if (mt == 1) MX4_INSTANCE(1);
+    else if (mt == 2) MX4_INSTANCE(2);
+    else MX4_INSTANCE(4);
+  });
+#undef MX4_INSTANCE
+#undef MX4_LAUNCH
+  HIP_CHECK_LAST();
+  return y;
+}
+
+}  // namespace
+
+// y = x @ dequant(codes, scales)^T (+ bias), 1 <= M <= 64, one launch.
+// waves / tiles: 0 = mxfp4_linear_instance's choice, otherwise forced
+// (benchmarks, tests).
+torch::Tensor mxfp4_linear(torch::Tensor x, torch::Tensor codes,
+                           torch::Tensor scales,
+                           c10::optional<torch::Tensor> bias, long waves,
+                           long tiles) {
+  return mx4_launch("mxfp4_linear", x, codes, scales, bias, nullptr, nullptr,
+                    c10::nullopt, waves, tiles);
+}
+
+// y[M,I] = silu(x @ dq(gate)^T (+ bias_gate)) * (x @ dq(up)^T (+ bias_up)),
+// M <= 64, one launch. tiles counts gate and up tiles of a wave: 2 or 4.
+torch::Tensor mxfp4_swiglu_linear(torch::Tensor x, torch::Tensor gate_codes,
+                                  torch::Tensor gate_scales,
+                                  torch::Tensor up_codes,
+                                  torch::Tensor up_scales,
+                                  c10::optional<torch::Tensor> bias_gate,
+                                  c10::optional<torch::Tensor> bias_up,
+                                  long waves, long tiles) {
+  return mx4_launch("mxfp4_swiglu_linear", x, gate_codes, gate_scales,
+                    bias_gate, &up_codes, &up_scales, bias_up, waves, tiles);
+}
+
+// [N, K] weight in bf16 or fp16 from codes [N, K/2] and scales [N, K/32].
+torch::Tensor mxfp4_dequantize(torch::Tensor codes, torch::Tensor scales,
+                               torch::ScalarType dtype) {
+  const bool fp16 = dtype == torch::kHalf;
+  TORCH_CHECK(fp16 || dtype == torch::kBFloat16,
+              "mxfp4_dequantize: dtype must be bf16 or fp16");
+  TORCH_CHECK(codes.is_cuda() && scales.is_cuda() &&
+                  codes.device() == scales.device(),
+              "mxfp4_dequantize: GPU tensors on one device required");
+  TORCH_CHECK(codes.dim() == 2 && scales.dim() == 2 &&
+                  codes.scalar_type() == torch::kByte &&
+                  scales.scalar_type() == torch::kByte &&
+                  codes.is_contiguous() && scales.is_contiguous(),
+              "mxfp4_dequantize: codes [N,K/2], scales [N,K/32], contiguous "
+              "uint8");
+  const long N = codes.size(0), K = codes.size(1) * 2;
+  TORCH_CHECK(N >= 1 && K >= MX4_GROUP && K % MX4_GROUP == 0 &&
+                  scales.size(0) == N && scales.size(1) * MX4_GROUP == K,
+              "mxfp4_dequantize: K must be a positive multiple of 32 and the "
+              "shapes must match");
+  TORCH_CHECK((uintptr_t)codes.data_ptr() % 16 == 0,
+              "mxfp4_dequantize: codes must be 16-byte aligned");
+  auto out = torch::empty({N, K}, codes.options().dtype(dtype));
+  const long groups = N * (K / MX4_GROUP);
+  TORCH_CHECK((groups + 255) / 256 < (1L << 31),
+              "mxfp4_dequantize: problem too large");
+  auto stream = at::hip::getCurrentHIPStream();
+  FP16_SWITCH(fp16, {
+    hipLaunchKernelGGL((mxfp4_dequantize_kernel<kFP16>),
+                       dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+                       stream, (const unsigned char*)codes.data_ptr(),
+                       (const unsigned char*)scales.data_ptr(),
+                       (short*)out.data_ptr(), groups);
+  });
+  HIP_CHECK_LAST();
+  return out;
+}

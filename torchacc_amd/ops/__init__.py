@@ -14,6 +14,10 @@ from .adamw import AdamW  # noqa: F401
 from .linear_fp8 import (Fp8Linear, Fp8SwiGLUMLP, fp8_linear,  # noqa: F401
                          fp8_swiglu_linear, quantize_model_fp8,
                          quantize_weight_fp8)
+from .linear_mxfp4 import (Mxfp4Linear, Mxfp4SwiGLUMLP,  # noqa: F401
+                           dequantize_weight_mxfp4, mxfp4_linear,
+                           mxfp4_swiglu_linear, quantize_model_mxfp4,
+                           quantize_weight_mxfp4)
 from .scaled_dot_product_attention import scaled_dot_product_attention  # noqa: F401
 
 from . import context_parallel  # noqa: F401
