@@ -40,13 +40,19 @@ def main():
     p.add_argument("--packed", action="store_true",
                    help="also time ContinuousBatcher(packed=True), "
                         "alternating with the padded engine")
-    p.add_argument("--weight-dtype", default="16bit", choices=["16bit", "fp8"],
+    p.add_argument("--weight-dtype", default="16bit",
+                   choices=["16bit", "fp8", "mxfp4"],
                    help="fp8: quantise the decoder projections to e4m3 "
-                        "weights (quantize_model_fp8) before serving")
+                        "weights (quantize_model_fp8) before serving; mxfp4: "
+                        "to MXFP4 weights (quantize_model_mxfp4)")
     p.add_argument("--fp8-gemm-max-m", type=int, default=None,
                    help="with fp8 weights: override ops.linear_fp8."
                         "FP8_GEMM_MAX_M; 64 sends every step above 64 rows "
                         "down the dequantise path, as before fp8_gemm")
+    p.add_argument("--mxfp4-gemm-max-m", type=int, default=None,
+                   help="with mxfp4 weights: override ops.linear_mxfp4."
+                        "MXFP4_GEMM_MAX_M; 64 sends every step above 64 rows "
+                        "down the dequantise path, as before mxfp4_gemm")
     args = p.parse_args()
 
     from torchacc_amd.models import (ContinuousBatcher, LlamaForCausalLM,
@@ -63,6 +69,11 @@ def main():
         linear_fp8.quantize_model_fp8(model)
         if args.fp8_gemm_max_m is not None:
             linear_fp8.FP8_GEMM_MAX_M = args.fp8_gemm_max_m
+    if args.weight_dtype == "mxfp4":
+        from torchacc_amd.ops import linear_mxfp4
+        linear_mxfp4.quantize_model_mxfp4(model)
+        if args.mxfp4_gemm_max_m is not None:
+            linear_mxfp4.MXFP4_GEMM_MAX_M = args.mxfp4_gemm_max_m
     gen = torch.Generator().manual_seed(0)
     lens = [int(x) for x in torch.linspace(16, 1024, REQUESTS).round()]
     order = torch.randperm(REQUESTS, generator=gen).tolist()
@@ -106,6 +117,7 @@ def main():
             "max_batch": MAX_BATCH, "prefill_chunk": args.prefill_chunk,
             "weight_dtype": args.weight_dtype,
             "fp8_gemm_max_m": args.fp8_gemm_max_m,
+            "mxfp4_gemm_max_m": args.mxfp4_gemm_max_m,
             "tokens_agree": f"{agree}/{REQUESTS * NEW}"}
     for name in fns:
         line[f"{name}_tok_s"] = round(statistics.median(samples[name]), 1)

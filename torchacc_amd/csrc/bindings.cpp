@@ -157,6 +157,18 @@ torch::Tensor mxfp4_dequantize(torch::Tensor codes, torch::Tensor scales,
                                torch::ScalarType dtype);
 std::vector<long> mxfp4_linear_instance(long n, long k, long num_cus,
                                         bool swiglu);
+// tiled variants for M > 64; num_splits: 0 = chosen from (M, N, K), CU count
+torch::Tensor mxfp4_gemm(torch::Tensor x, torch::Tensor codes,
+                         torch::Tensor scales,
+                         c10::optional<torch::Tensor> bias, long num_splits);
+torch::Tensor mxfp4_swiglu_gemm(torch::Tensor x, torch::Tensor gate_codes,
+                                torch::Tensor gate_scales,
+                                torch::Tensor up_codes,
+                                torch::Tensor up_scales,
+                                c10::optional<torch::Tensor> bias_gate,
+                                c10::optional<torch::Tensor> bias_up,
+                                long num_splits);
+long mxfp4_gemm_num_splits(long m, long n, long k, long num_cus);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "torchacc_amd CDNA4 (gfx950) kernels";
@@ -218,4 +230,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("waves") = 0, pybind11::arg("tiles") = 0);
   m.def("mxfp4_dequantize", &mxfp4_dequantize);
   m.def("mxfp4_linear_instance", &mxfp4_linear_instance);
+  m.def("mxfp4_gemm", &mxfp4_gemm, pybind11::arg("x"), pybind11::arg("codes"),
+        pybind11::arg("scales"), pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("num_splits") = 0);
+  m.def("mxfp4_swiglu_gemm", &mxfp4_swiglu_gemm, pybind11::arg("x"),
+        pybind11::arg("gate_codes"), pybind11::arg("gate_scales"),
+        pybind11::arg("up_codes"), pybind11::arg("up_scales"),
+        pybind11::arg("bias_gate") = pybind11::none(),
+        pybind11::arg("bias_up") = pybind11::none(),
+        pybind11::arg("num_splits") = 0);
+  m.def("mxfp4_gemm_num_splits", &mxfp4_gemm_num_splits);
 }

@@ -63,7 +63,9 @@
 // contributes zeros and reads its scale bytes one by one, predicated.
 //
 // mxfp4_dequantize further down writes the [N, K] 16-bit weight with the same
-// convert (16-byte loads and stores); it serves M > 64 and checkpoint export.
+// convert (16-byte loads and stores); it serves checkpoint export and the row
+// counts beyond the tiled mxfp4_gemm kernel (second half of this file), which
+// serves M > 64.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -329,6 +331,342 @@ void mxfp4_dequantize_kernel(const unsigned char* __restrict__ codes,
         mx4_cvt8<FP16>(c[s], sc);
 }
 
+// ---------------------------------------------------------------------------
+// mxfp4_gemm: the same formula for M > 64 (prefill, mixed serving steps) as a
+// tiled GEMM that keeps the codes PACKED in LDS and converts them after the
+// fragment read.
+//
+// A workgroup of 4 waves computes 128 x rows by 128 weight (A) rows over
+// BK = 64 codes (two scale groups) per stage; the waves sit 2 (channels) x 2
+// (rows), each on 64 x 64 as 2 x 2 tiles of v_mfma_f32_32x32x16_{bf16,f16}.
+// The weights are the A operand, so the result is y^T: lane l owns x row l&31
+// of a tile and, per group of four accumulator registers q, the four
+// consecutive channels 8q + 4(l>>5)..+3: the epilogue is mx4_finish4.
+//
+// LDS, per stage 20 KiB, MX4G_STAGES = 3 of them (60 KiB, two workgroups per
+// CU); both images are filled global -> LDS directly (attn_glds16, five per
+// thread and stage), with the swizzles on the source address:
+//   x      [128 rows][64 x 16 bit], 128-byte rows whose eight 16-byte chunks
+//          are XORed with (row>>1)&7 (fp8_gemm's image). The fragment of
+//          K-step s is chunk 4*hi + s of row l&31 (hi = l>>5): the reduction
+//          order inside a stage follows the weight side, as in the skinny
+//          kernel.
+//   codes  [128 rows][32 bytes]: 256 slots of 16 bytes, one per thread; a
+//          slot is 32 codes, one scale group. Group `half` of row r sits in
+//          slot 2r + (half ^ ((r>>3)&1)). A lane's A fragment for the WHOLE
+//          stage is one ds_read_b128 of slot (row l&31, half hi); its 16-lane
+//          groups are rows 16n..16n+15 of one half, and the XOR sends rows
+//          8..15 to the other slot parity: 16 distinct slots of the 256-byte
+//          bank line (unswizzled, 2r + hi has 8 distinct values mod 16, a
+//          2-way conflict). Dword s of the slot feeds K-step s through
+//          mx4_cvt8 (exact): 2 reads and 32 converts per lane under 16 MFMAs;
+//          a code is converted once per wave, twice per workgroup.
+//   scales a lane needs scales[row][2t + hi] of its two channel tiles: two
+//          byte loads per stage, issued a stage ahead into registers (rows
+//          start at any byte). No LDS image: the bytes are per lane already,
+//          and an image would add a sixth direct load whose 128 live bytes
+//          use an eighth of a wave instruction.
+// Pipeline: the direct loads of step t+2 are issued after the barrier of step
+// t, which also retires every read of the buffer they overwrite (step t-1's).
+// Loads complete in order, so waiting until at most the MX4G_LOADS loads of
+// step t+1 are outstanding (vmcnt) publishes step t; one barrier per stage.
+//
+// SWIGLU: two code and two scale pointers, nothing re-laid. A workgroup's 128
+// A rows are 64 gate channels and the same 64 up channels; a wave's tile
+// i = 0 is gate and i = 1 up for the SAME 32 channels, so
+// silu(g (+ bg)) * (u (+ bu)) is formed in-lane in fp32, g and u never reach
+// memory and x is staged once for both. grid.x = ceil(I / 64).
+//
+// Tails: rows >= M read row M-1 and are never stored; channels >= N read row
+// N-1 and are predicated at the store. The one ragged step (K % 64 == 32) is
+// always the last: x goes through registers with chunks at or past K zeroed;
+// both code slots of a row are filled from its group 0 (no load leaves the
+// tensor), and lanes of half 1 zero their fragment and read scale 1.
+//
+// Split-K: where the tiles are fewer than the CUs, K is cut over grid.z into
+// contiguous, balanced runs of steps; fp32 partials [S][M][N] (SWIGLU:
+// [S][2][M][I]) are summed in split order by mxfp4_gemm_combine_kernel, which
+// applies the epilogue. No atomics: bits depend on (M, N, K, CU count) only.
+// S depends on M, so unlike the skinny kernel this path does NOT promise that
+// a row's bits are independent of the batch it sits in.
+// -DMX4G_STAGES=2 builds the two-stage variant timed in
+// profiles/r20_mxfp4_gemm.md
+#ifndef MX4G_STAGES
+#define MX4G_STAGES 3
+#endif
+constexpr int MX4G_BM = 128;      // x rows per workgroup
+constexpr int MX4G_BA = 128;      // weight (A) rows per workgroup
+constexpr int MX4G_BK = 64;       // codes per stage
+constexpr int MX4G_X_B = MX4G_BM * MX4G_BK * 2;      // x image
+constexpr int MX4G_W_B = MX4G_BA * MX4G_BK / 2;      // packed code image
+constexpr int MX4G_STAGE_B = MX4G_X_B + MX4G_W_B;
+constexpr int MX4G_LOADS = 5;     // direct loads per thread and full stage
+constexpr int MX4G_MAX_SPLITS = 16;
+// BK steps a split keeps at least when S is chosen automatically
+constexpr int MX4G_MIN_STEPS = 4;
+static_assert(MX4G_STAGES == 2 || MX4G_STAGES == 3, "two or three stages");
+static_assert(MX4G_STAGES * MX4G_STAGE_B <= 64 * 1024, "LDS");
+
+// byte offset of 16-byte chunk ch (0..7) of row `row` in the x image
+DEVINLINE constexpr unsigned mx4g_xoff(int row, int ch) {
+  return (unsigned)(row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
+}
+// byte offset of scale group `half` (0..1) of row `row` in the code image
+DEVINLINE constexpr unsigned mx4g_woff(int row, int half) {
+  return (unsigned)((2 * row + (half ^ ((row >> 3) & 1))) << 4);
+}
+
+template <bool FP16>
+DEVINLINE f32x16 mx4g_mfma(attn_u32x4 a, attn_u32x4 b, f32x16 c) {
+  if constexpr (FP16) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(
+        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
+        c, 0, 0, 0);
+  } else {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+        __builtin_bit_cast(mx4_bf16x8, a), __builtin_bit_cast(mx4_bf16x8, b),
+        c, 0, 0, 0);
+  }
+}
+
+// Wait until at most `PENDING` of this wave's loads are outstanding (vmcnt;
+// 0x0F70 waits for nothing else), then a workgroup barrier with its LDS
+// fences written out.
+template <int PENDING>
+DEVINLINE void mx4g_publish() {
+  static_assert(PENDING >= 0 && PENDING < 16, "vmcnt's low field");
+  __builtin_amdgcn_s_waitcnt(0x0F70 | PENDING);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// grid = (ceil(N / BN), ceil(M / 128), S), BN = 128 (PLAIN) or 64 (SWIGLU);
+// block = 256. PLAIN reads (w0, s0, b0) only. S == 1: writes y. S > 1: writes
+// raw fp32 sums to part[S][M][N] (SWIGLU: part[S][2][M][N], gate then up).
+template <bool FP16, bool SWIGLU>
+__global__ __launch_bounds__(256, 2)
+void mxfp4_gemm_kernel(const short* __restrict__ x,
+                       const unsigned char* __restrict__ w0,
+                       const unsigned char* __restrict__ w1,
+                       const unsigned char* __restrict__ s0,
+                       const unsigned char* __restrict__ s1,
+                       const short* __restrict__ b0,
+                       const short* __restrict__ b1,
+                       short* __restrict__ y, float* __restrict__ part,
+                       int M, int N, int K) {
+  constexpr int NS = MX4G_STAGES;
+  constexpr int BN = SWIGLU ? MX4G_BA / 2 : MX4G_BA;
+  __shared__ __attribute__((aligned(16))) char lds[NS * MX4G_STAGE_B];
+  const int tid = threadIdx.x, lane = tid % WAVE;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int wn = wave & 1, wm = wave >> 1;
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int n0 = blockIdx.x * BN, m0 = blockIdx.y * MX4G_BM;
+  const int split = blockIdx.z, S = gridDim.z;
+  const int G = K / MX4_GROUP;    // scale bytes per row
+
+  // contiguous, balanced runs of BK steps over the splits; the host keeps
+  // S <= max(1, K / BK), so every split owns at least one step
+  const int T = (K + MX4G_BK - 1) / MX4G_BK, Tfull = K / MX4G_BK;
+  const int t0 = (int)((long)split * T / S);
+  const int t1 = (int)((long)(split + 1) * T / S);
+  // steps below tq have a full successor NS - 2 steps on
+  const int tq = min(t1, Tfull) - (NS - 2);
+
+  // A row r of the workgroup: PLAIN channel n0 + r of w0. SWIGLU: wave half
+  // r>>6, tile (r>>5)&1 = gate / up, channel n0 + 32 * (r>>6) + (r&31).
+  auto a_chan = [&](int r) {
+    return min(SWIGLU ? n0 + (r >> 6) * 32 + (r & 31) : n0 + r, N - 1);
+  };
+
+  // x staging: pass i fills slots i*256 + tid of the image, slot s = row
+  // s>>3, stored chunk s&7, which holds logical chunk (s&7) ^ ((row>>1)&7);
+  // the row's bits 1..3 are tid's bits 4..6 in every pass
+  const int xc = (tid & 7) ^ ((tid >> 4) & 7);
+  const short* xsrc[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    xsrc[i] = x + (long)min(m0 + i * 32 + (tid >> 3), M - 1) * K + xc * 8;
+  // code staging: thread tid fills slot tid = 2 * row + stored parity, which
+  // holds group parity ^ ((row>>3)&1); the row's bit 3 is tid's bit 4
+  const int wr = tid >> 1;
+  const int wh = (tid & 1) ^ ((tid >> 4) & 1);
+  const unsigned char* wsrc =
+      (SWIGLU && ((wr >> 5) & 1) ? w1 : w0) + (long)a_chan(wr) * (K / 2);
+  // scale rows of the lane's two channel tiles
+  const unsigned char* srow[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    srow[i] = (SWIGLU && i ? s1 : s0) +
+              (long)a_chan(wn * 64 + i * 32 + l31) * G;
+
+  // the lane's scale bytes of step t; groups at or past K read as 1.0
+  auto load_scales = [&](int t, unsigned (&e)[2]) {
+    const int gi = 2 * t + hi;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      e[i] = 127u;
+      if (gi < G) e[i] = srow[i][gi];
+    }
+  };
+  // issue the loads of step t into buffer `buf`
+  auto stage_load = [&](int t, int buf) {
+    const int k0 = t * MX4G_BK;
+    char* xi = lds + buf * MX4G_STAGE_B;
+    char* wi = xi + MX4G_X_B + wave * WAVE * 16;
+    if (t < Tfull) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        attn_glds16(xsrc[i] + k0, xi + (i * 256 + wave * WAVE) * 16);
+      attn_glds16(wsrc + (k0 >> 1) + wh * 16, wi);
+    } else {
+      const bool live = k0 + xc * 8 < K;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        attn_u32x4 v = attn_u32x4{0u, 0u, 0u, 0u};
+        if (live) v = *reinterpret_cast<const attn_u32x4*>(xsrc[i] + k0);
+        *reinterpret_cast<attn_u32x4*>(xi + (i * 256 + tid) * 16) = v;
+      }
+      // group 1 lies past the row: both slots take group 0
+      attn_glds16(wsrc + (k0 >> 1), wi);
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // en: the scale bytes of the next step, requested at the top of a step and
+  // converted at its end; sc: the current step's scales
+  unsigned en[2];
+  load_scales(t0, en);
+  float sc[2] = {mx4_scale(en[0]), mx4_scale(en[1])};
+#pragma unroll
+  for (int d = 0; d < NS - 1; ++d)
+    if (t0 + d < t1) stage_load(t0 + d, d);
+
+  // fragment reads: x row 32j + l31 of the wave's half, chunk 4hi + s; code
+  // slot (row 32i + l31 of the wave's half, group hi)
+  const unsigned sw = (unsigned)((l31 >> 1) & 7);
+  const unsigned xrow_off = (unsigned)((wm * 64 + l31) * 128);
+  const unsigned wslot_off =
+      (unsigned)MX4G_X_B + mx4g_woff(wn * 64 + l31, hi);
+
+  int cur = 0;
+  for (int t = t0; t < t1; ++t) {
+    // publishes step t; retires the reads of step t-1's buffer
+    if (NS > 2 && t < tq) mx4g_publish<(NS - 2) * MX4G_LOADS>();
+    else mx4g_publish<0>();
+    if (t + 1 < t1) load_scales(t + 1, en);
+    if (t + NS - 1 < t1) {
+      const int nb = cur + NS - 1;
+      stage_load(t + NS - 1, nb >= NS ? nb - NS : nb);
+    }
+    const char* base = lds + cur * MX4G_STAGE_B;
+    attn_u32x4 wf[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      wf[i] = *reinterpret_cast<const attn_u32x4*>(
+          base + wslot_off + i * (32 * 32));
+      if (2 * t + hi >= G) wf[i] = attn_u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const unsigned ch = (((unsigned)(4 * hi + s)) ^ sw) << 4;
+      attn_u32x4 a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        a[i] = mx4_cvt8<FP16>(wf[i][s], sc[i]);
+        b[i] = *reinterpret_cast<const attn_u32x4*>(
+            base + xrow_off + i * (32 * 128) + ch);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = mx4g_mfma<FP16>(a[i], b[j], acc[i][j]);
+    }
+    sc[0] = mx4_scale(en[0]);
+    sc[1] = mx4_scale(en[1]);
+    cur = cur + 1 == NS ? 0 : cur + 1;
+  }
+
+  // lane: x row m of tile j; registers 4q..4q+3 of tile i: channels n..n+3.
+  // SWIGLU: tile 0 is gate and tile 1 up of the same channels.
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = m0 + wm * 64 + j * 32 + l31;
+    if (m >= M) continue;
+#pragma unroll
+    for (int i = 0; i < (SWIGLU ? 1 : 2); ++i) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + wn * (BN / 2) + i * 32 + 8 * q + 4 * hi;
+        if (n >= N) continue;
+        f32x4 v[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int ti = SWIGLU ? h : i;
+          v[h] = f32x4{acc[ti][j][4 * q], acc[ti][j][4 * q + 1],
+                       acc[ti][j][4 * q + 2], acc[ti][j][4 * q + 3]};
+        }
+        if (S == 1) {
+          mx4_finish4<FP16, SWIGLU>(v[0], v[1], m, n, N, b0, b1, y);
+          continue;
+        }
+#pragma unroll
+        for (int h = 0; h < (SWIGLU ? 2 : 1); ++h) {
+          float* p = part +
+                     (((long)split * (SWIGLU ? 2 : 1) + h) * M + m) * N + n;
+          if ((N & 3) == 0) {
+            *reinterpret_cast<f32x4*>(p) = v[h];
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (n + r < N) p[r] = v[h][r];
+          }
+        }
+      }
+    }
+  }
+}
+
+// y = epilogue(sum over splits, in split order); a thread per four channels
+// of one row. part is [S][M][N], SWIGLU [S][2][M][N].
+template <bool FP16, bool SWIGLU>
+__global__ __launch_bounds__(256)
+void mxfp4_gemm_combine_kernel(const float* __restrict__ part,
+                               const short* __restrict__ b0,
+                               const short* __restrict__ b1,
+                               short* __restrict__ y, int M, int N, int S) {
+  constexpr int P = SWIGLU ? 2 : 1;
+  const int n4 = (N + 3) / 4;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)M * n4) return;
+  const long m = idx / n4;
+  const int n = (int)(idx % n4) * 4;
+  f32x4 v[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  for (int s = 0; s < S; ++s) {
+#pragma unroll
+    for (int h = 0; h < P; ++h) {
+      const float* p = part + (((long)s * P + h) * M + m) * N + n;
+      if ((N & 3) == 0) {
+        v[h] += *reinterpret_cast<const f32x4*>(p);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < N) v[h][r] += p[r];
+      }
+    }
+  }
+  mx4_finish4<FP16, SWIGLU>(v[0], v[1], m, n, N, b0, b1, y);
+}
+
 }  // namespace
 
 #pragma clang attribute pop
@@ -529,4 +867,135 @@ torch::Tensor mxfp4_dequantize(torch::Tensor codes, torch::Tensor scales,
   });
   HIP_CHECK_LAST();
   return out;
+}
+
+// ---------------------------------------------------------------------------
+// mxfp4_gemm host side.
+
+namespace {
+
+// K splits for row tiles of 128 and channel tiles of bn: fp8_gemm_num_splits'
+// rule. 1 once the tiles cover the CUs, otherwise as many as bring the
+// workgroup count up to the CU count, while every split keeps at least
+// MX4G_MIN_STEPS whole BK steps.
+long mx4g_splits(long m, long n, long k, long num_cus, long bn) {
+  const long tiles = ((m + MX4G_BM - 1) / MX4G_BM) * ((n + bn - 1) / bn);
+  const long steps = k / MX4G_BK;   // whole steps
+  const long want = num_cus / tiles;
+  const long cap = std::min<long>(MX4G_MAX_SPLITS, steps / MX4G_MIN_STEPS);
+  return std::max<long>(1, std::min(want, cap));
+}
+
+// Shared front end: PLAIN when c1 is absent, SWIGLU otherwise.
+torch::Tensor mx4g_launch(const char* op, torch::Tensor x, torch::Tensor c0,
+                          torch::Tensor s0, c10::optional<torch::Tensor> b0,
+                          const torch::Tensor* c1, const torch::Tensor* s1,
+                          c10::optional<torch::Tensor> b1, long num_splits) {
+  const bool swiglu = c1 != nullptr;
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+                  (uintptr_t)x.data_ptr() % 16 == 0,
+              op, ": x must be a contiguous, aligned [M,K] GPU tensor");
+  const bool fp16 = x.scalar_type() == torch::kHalf;
+  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
+              op, ": x must be bf16 or fp16");
+  const long M = x.size(0), K = x.size(1);
+  TORCH_CHECK(K >= MX4_GROUP && K % MX4_GROUP == 0,
+              op, ": K must be a positive multiple of 32");
+  mx4_check(op, x, c0, s0, b0);
+  if (swiglu) {
+    mx4_check(op, x, *c1, *s1, b1);
+    TORCH_CHECK(c1->size(0) == c0.size(0), op, ": gate/up shape mismatch");
+  }
+  const long N = c0.size(0);
+  const long row_tiles = (M + MX4G_BM - 1) / MX4G_BM;
+  TORCH_CHECK(M >= 1 && N >= 1 && M * K < (1L << 31) &&
+                  (M + MX4G_BM) * N < (1L << 31) && row_tiles <= 65535,
+              op, ": problem too large");
+
+  const long bn = swiglu ? MX4G_BA / 2 : MX4G_BA;
+  long S = num_splits;
+  if (S <= 0) {
+    S = mx4g_splits(
+        M, N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
+        bn);
+  }
+  TORCH_CHECK(S <= MX4G_MAX_SPLITS, op, ": num_splits above ",
+              MX4G_MAX_SPLITS);
+  // every split keeps at least one whole BK step
+  S = std::max<long>(1, std::min(S, K / MX4G_BK));
+
+  auto y = torch::empty({M, N}, x.options());
+  torch::Tensor part;
+  float* part_p = nullptr;
+  if (S > 1) {
+    part = torch::empty({S * (swiglu ? 2 : 1), M, N},
+                        x.options().dtype(torch::kFloat));
+    part_p = part.data_ptr<float>();
+  }
+  auto stream = at::hip::getCurrentHIPStream();
+  const dim3 grid((unsigned)((N + bn - 1) / bn), (unsigned)row_tiles,
+                  (unsigned)S);
+  const long groups = M * ((N + 3) / 4);
+  auto bp = [](const c10::optional<torch::Tensor>& b) {
+    return b.has_value() ? (const short*)b->data_ptr() : nullptr;
+  };
+#define MX4G_LAUNCH(SW)                                                       \
+  do {                                                                        \
+    hipLaunchKernelGGL((mxfp4_gemm_kernel<kFP16, SW>), grid, dim3(256), 0,    \
+                       stream, (const short*)x.data_ptr(),                    \
+                       (const unsigned char*)c0.data_ptr(),                   \
+                       SW ? (const unsigned char*)c1->data_ptr() : nullptr,   \
+                       (const unsigned char*)s0.data_ptr(),                   \
+                       SW ? (const unsigned char*)s1->data_ptr() : nullptr,   \
+                       bp(b0), bp(b1), (short*)y.data_ptr(), part_p, (int)M,  \
+                       (int)N, (int)K);                                       \
+    HIP_CHECK_LAST();                                                         \
+    if (S > 1) {                                                              \
+      hipLaunchKernelGGL((mxfp4_gemm_combine_kernel<kFP16, SW>),              \
+                         dim3((unsigned)((groups + 255) / 256)), dim3(256),   \
+                         0, stream, part_p, bp(b0), bp(b1),                   \
+                         (short*)y.data_ptr(), (int)M, (int)N, (int)S);       \
+      HIP_CHECK_LAST();                                                       \
+    }                                                                         \
+  } while (0)
+  FP16_SWITCH(fp16, {
+    if (swiglu) MX4G_LAUNCH(true);
+    else MX4G_LAUNCH(false);
+  });
+#undef MX4G_LAUNCH
+  return y;
+}
+
+}  // namespace
+
+// Number of K splits of mxfp4_gemm for an [M, K] x [N, K]^T problem on a
+// device with num_cus compute units (fp8_gemm_num_splits' rule on 128 x 128
+// tiles; mxfp4_swiglu_gemm applies it to its 128 x 64 tiles).
+long mxfp4_gemm_num_splits(long m, long n, long k, long num_cus) {
+  return mx4g_splits(m, n, k, num_cus, MX4G_BA);
+}
+
+// y = x @ dequant(codes, scales)^T (+ bias) for any M >= 1, on the tiled
+// kernel. num_splits: 0 = chosen from (M, N, K) and the CU count, otherwise
+// forced (benchmarks, tests). Bitwise repeatable; NOT batch-invariant, since
+// the split depends on M.
+torch::Tensor mxfp4_gemm(torch::Tensor x, torch::Tensor codes,
+                         torch::Tensor scales,
+                         c10::optional<torch::Tensor> bias, long num_splits) {
+  return mx4g_launch("mxfp4_gemm", x, codes, scales, bias, nullptr, nullptr,
+                     c10::nullopt, num_splits);
+}
+
+// y[M,I] = silu(x @ dq(gate)^T (+ bias_gate)) * (x @ dq(up)^T (+ bias_up)) for
+// any M >= 1, one launch of the tiled kernel (plus the combine when K is
+// split). Bitwise repeatable; NOT batch-invariant.
+torch::Tensor mxfp4_swiglu_gemm(torch::Tensor x, torch::Tensor gate_codes,
+                                torch::Tensor gate_scales,
+                                torch::Tensor up_codes,
+                                torch::Tensor up_scales,
+                                c10::optional<torch::Tensor> bias_gate,
+                                c10::optional<torch::Tensor> bias_up,
+                                long num_splits) {
+  return mx4g_launch("mxfp4_swiglu_gemm", x, gate_codes, gate_scales,
+                     bias_gate, &up_codes, &up_scales, bias_up, num_splits);
 }

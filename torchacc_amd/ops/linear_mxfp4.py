@@ -21,7 +21,11 @@ weights of magnitude 2^-12 .. 2^14 per group); it is not checked per call.
 The only approximation is the one-off rounding in ``quantize_weight_mxfp4``:
 ``mxfp4_linear`` computes ``x @ dequant(codes, scales)^T + bias`` with fp32
 accumulation on the ``_C.mxfp4_linear`` MFMA kernel (csrc/mxfp4_linear.hip),
-one launch for every (N, K), for decode-sized batches.
+one launch for every (N, K), for decode-sized batches, and on the tiled
+``_C.mxfp4_gemm`` kernel of the same file above them (prefill, chunked prefill
+and mixed serving steps), which keeps the codes packed in LDS and converts
+them after the fragment read; ``_C.mxfp4_swiglu_gemm`` is its fused gate/up
+instance.
 
 Inference only.
 """
@@ -37,10 +41,23 @@ from .swiglu import swiglu
 
 MXFP4_GROUP = 32
 
-# Rows up to which GPU inputs take the one-launch kernel. Above it the weight
-# is dequantised in memory (mxfp4_dequantize, a 16-bit N*K transient) and the
-# 16-bit GEMM runs.
+# Rows up to which GPU inputs take the one-launch kernel. Above it the tiled
+# mxfp4_gemm kernel runs, see MXFP4_GEMM_MAX_M.
 MXFP4_LINEAR_MAX_M = 64
+
+# Rows up to which GPU inputs above MXFP4_LINEAR_MAX_M take the tiled
+# mxfp4_gemm / mxfp4_swiglu_gemm kernels (None: no limit). Above it the weight
+# is dequantised in memory (mxfp4_dequantize, a 16-bit N*K transient) and the
+# 16-bit GEMM runs (the only path there before mxfp4_gemm).
+# Measured (profiles/r20_mxfp4_gemm.md, eight projection / LM-head shapes, time
+# of mxfp4_gemm over time of the dequantise path, 16-bit spread <= 1.4% except
+# one 7% row):
+#   M = 128   0.30 - 0.75      M = 1024  0.94 - 1.33 (loses at seven shapes)
+#   M = 256   0.53 - 1.00      M = 2048  1.09 - 1.47
+#   M = 512   0.80 - 0.91      M = 4096  0.98 - 1.68
+# 512 is the largest benchmarked M at which every shape wins by more than the
+# spread (at M = 256 the 1024 x 4096 shape is level, inside its spread).
+MXFP4_GEMM_MAX_M = 512
 
 # value of code c (bit 3 = sign)
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0,
@@ -120,9 +137,11 @@ def mxfp4_linear(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
 
     On a GPU, up to ``MXFP4_LINEAR_MAX_M`` rows are one launch of the MXFP4
     kernel: the result is bitwise repeatable and a row's bits do not depend on
-    the batch it sits in. Above it the weight is dequantised by
-    ``_C.mxfp4_dequantize`` into a 16-bit N*K transient and ``tuned_linear``
-    runs on it."""
+    the batch it sits in. Above it, up to ``MXFP4_GEMM_MAX_M`` rows run on the
+    tiled ``_C.mxfp4_gemm`` kernel: bitwise repeatable, but NOT
+    batch-invariant (its K split depends on the row count). Above that the
+    weight is dequantised by ``_C.mxfp4_dequantize`` into a 16-bit N*K
+    transient and ``tuned_linear`` runs on it."""
     _refuse_grad("mxfp4_linear", x, bias)
     _check_k(x.shape[-1], "mxfp4_linear")
     ext = dispatch(x)
@@ -136,6 +155,8 @@ def mxfp4_linear(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
         out = out.to(x.dtype)
     elif x2d.shape[0] <= MXFP4_LINEAR_MAX_M:
         out = ext.mxfp4_linear(x2d.contiguous(), codes, scales, bias)
+    elif MXFP4_GEMM_MAX_M is None or x2d.shape[0] <= MXFP4_GEMM_MAX_M:
+        out = ext.mxfp4_gemm(x2d.contiguous(), codes, scales, bias)
     else:
         out = tuned_linear(x2d, ext.mxfp4_dequantize(codes, scales, x.dtype),
                            bias)
@@ -154,7 +175,9 @@ def mxfp4_swiglu_linear(x: torch.Tensor, gate_codes: torch.Tensor,
     On a GPU, up to ``MXFP4_LINEAR_MAX_M`` rows are ONE launch of the fused
     kernel: gate and up pre-activations stay fp32 and never reach memory, and
     the result is bitwise repeatable and independent of the batch a row sits
-    in. Above it, two ``mxfp4_linear`` calls and ``swiglu``."""
+    in. Above it, up to ``MXFP4_GEMM_MAX_M`` rows run on the tiled
+    ``_C.mxfp4_swiglu_gemm`` kernel, which keeps both properties except batch
+    invariance. Above that, two ``mxfp4_linear`` calls and ``swiglu``."""
     _refuse_grad("mxfp4_swiglu_linear", x, bias_gate, bias_up)
     _check_k(x.shape[-1], "mxfp4_swiglu_linear")
     ext = dispatch(x)
@@ -175,6 +198,9 @@ def mxfp4_swiglu_linear(x: torch.Tensor, gate_codes: torch.Tensor,
         out = ext.mxfp4_swiglu_linear(x2d.contiguous(), gate_codes,
                                       gate_scales, up_codes, up_scales,
                                       bias_gate, bias_up)
+    elif MXFP4_GEMM_MAX_M is None or x2d.shape[0] <= MXFP4_GEMM_MAX_M:
+        out = ext.mxfp4_swiglu_gemm(x2d.contiguous(), gate_codes, gate_scales,
+                                    up_codes, up_scales, bias_gate, bias_up)
     else:
         out = swiglu(mxfp4_linear(x2d, gate_codes, gate_scales, bias_gate),
                      mxfp4_linear(x2d, up_codes, up_scales, bias_up))
