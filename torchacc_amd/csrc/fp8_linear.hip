@@ -1,60 +1,41 @@
-// Weight-only fp8 (e4m3) linear layer for decode-sized batches (W8A16):
+// Weight-only fp8 (e4m3) linear layers (W8A16):
 //   y[M,N] = (x[M,K] @ dequant(W8[N,K])^T) * scale[N] (+ bias[N])
-// x, y bf16 or fp16; W8 e4m3 codes, row-major; one fp32 scale per output
-// channel. A decode step is bound by reading the projection weights once;
-// e4m3 halves those bytes against the 16-bit paths in gemm.hip.
+// W8 e4m3 codes, row-major; one fp32 scale per output channel, which
+// multiplies the fp32 accumulator once, in the epilogue. A decode step is
+// bound by reading the projection weights once; e4m3 halves those bytes
+// against the 16-bit paths in gemm.hip. Operand order, batch invariance and
+// tail rules are in wq_gemm_common.h, whose host front end (operand checks,
+// split rule, allocate / launch / combine), MFMA wrappers, x-image layout and
+// stage barrier this file uses; its kernels are its own (folded onto the
+// shared frame and epilogue they ran 1-7 % slower,
+// profiles/r21_wq_gemm_refactor.md).
 //
-// Matrix instruction: v_mfma_f32_16x16x32_{bf16,f16} with the WEIGHTS as the
-// A operand (16 output channels per tile, lane l holds row l&15, k-slots
-// 8*(l>>4)..+7) and up to 16 activation rows as the B operand (lane l holds
-// column l&15). The result is y^T: lane l owns activation row l&15 and the
-// four consecutive channels 4*(l>>4)..+3, which is an 8-byte store along N.
-// A wave owns NT = 2 channel tiles and MT in {1,2,4} column blocks; one
-// converted A fragment feeds MT MFMAs and one B fragment feeds NT.
-//
-// Weight stream: a lane reads 16 contiguous codes of its row per 16-byte
-// load; the four lane groups of a row cover 64 contiguous bytes, and a step
-// issues the two loads of a 128-byte line back to back. The 16 codes feed two
-// MFMA K-steps (codes 0..7, then 8..15). The reduction order inside K is
-// free, so the x fragment simply follows the same permutation: lane (j, g)
-// reads x[j][k0 + 16g + 8s .. +7] for K-step s, 32 contiguous bytes.
+// Skinny weight stream (v_mfma_f32_16x16x32: lane l holds weight row l&15,
+// k-slots 8*(l>>4)..+7): a lane reads 16 contiguous codes of its row per
+// 16-byte load; the four lane groups of a row cover 64 contiguous bytes, and a
+// step issues the two loads of a 128-byte line back to back: 128 codes per
+// row and step. The 16 codes feed two MFMA K-steps (codes 0..7, then 8..15).
+// The reduction order inside K is free, so the x fragment simply follows the
+// same permutation: lane (j, g) reads x[j][k0 + 16g + 8s .. +7] for K-step s,
+// 32 contiguous bytes.
 //
 // e4m3 -> 16 bit is exact (3 mantissa bits): v_cvt_pk_f32_fp8, then
-// v_cvt_pk_bf16_f32 (bf16) or v_cvt_pkrtz (fp16). The channel scale
-// multiplies the fp32 accumulator once, in the epilogue.
+// v_cvt_pk_bf16_f32 (bf16) or v_cvt_pkrtz (fp16).
 //
-// Filling the device: a workgroup is 4 waves on the same 32 channels, each
-// wave on its own contiguous run of 128-code steps; the four accumulators are
-// summed through LDS in wave order. Where N/32 workgroups are too few, K is
-// also cut across S workgroups (grid.y) that write fp32 partials, summed in
-// split order by a second launch (the split-KV combine pattern). No atomics.
-// S and every K boundary come from (N, K) and the CU count alone, never from
-// M, and an output row depends on its own B column only: a row's bits do not
-// depend on the batch it sits in, nor on its position.
-//
-// Activations are read straight from global memory (they are L2-resident).
-// With K split across the waves of a workgroup no two waves read the same x
-// bytes, so an LDS stage could not cut the traffic and would put a barrier
-// per chunk on the weight stream (profiles/r15_fp8_linear.md). Rows >= M are
-// read from row M-1 and never stored, so the MFMA path has no predicate.
-//
-// fp8_wide further down is the same body in one launch for every (N, K): K is
-// cut only across the 4 or 8 waves of a workgroup on 16 or 32 channels, with
-// a plain epilogue and a fused gate/up SwiGLU one (opt-in, one_launch=True).
-//
-// M > 64 (prefill, mixed serving steps) is served by fp8_gemm further down, a
-// 128 x 128 tiled kernel on the 32x32x16 MFMA that stages both operands in
-// LDS. It is bitwise repeatable and depends on (M, N, K, CU count) only, but
-// its K split depends on M: the batch invariance above holds for fp8_linear
-// (M <= 64) alone.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <algorithm>
+// Three ways to fill the device:
+//   fp8_linear         4 waves on 32 channels; where N/32 workgroups are too
+//                      few, K is also cut across S workgroups that write fp32
+//                      partials, summed by a second launch (the split-KV
+//                      combine pattern). Any M, in 64-row blocks.
+//   fp8_linear_wide,   ONE launch for every (N, K), M <= 64: at batch 1 a
+//   fp8_swiglu_linear  layer's projections are bound by launch count, not
+//                      bytes (profiles/r17_fp8_one_launch.md), so K is cut
+//                      only across the 4 or 8 waves of a workgroup on 16 or 32
+//                      channels (opt-in, one_launch=True).
+//   fp8_gemm           M > 64 (prefill, mixed serving steps), further down.
 #include <vector>
 
-#include "common.h"
-#include "attn_common.h"
+#include "wq_gemm_common.h"
 
 // packed fp32 VALU forms are kept out of this file's device code
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
@@ -71,9 +52,6 @@ constexpr int FP8L_MAX_SPLITS = 16;
 // loads in flight each (profiles/r15_fp8_linear.md)
 constexpr int FP8L_WG_PER_CU = 2;
 
-typedef __bf16 fp8l_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fp8l_bf16x2 __attribute__((ext_vector_type(2)));
-
 template <bool FP16>
 struct Fp8lElem;
 
@@ -85,12 +63,7 @@ struct Fp8lElem<false> {
   // the convert's result pair twice, so the float-domain convert is used.
   static DEVINLINE unsigned pack(f32x2 f) {
     return __builtin_bit_cast(unsigned,
-                              __builtin_convertvector(f, fp8l_bf16x2));
-  }
-  static DEVINLINE f32x4 mfma(attn_u32x4 a, attn_u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-        __builtin_bit_cast(fp8l_bf16x8, a), __builtin_bit_cast(fp8l_bf16x8, b),
-        c, 0, 0, 0);
+                              __builtin_convertvector(f, wq_bf16x2));
   }
 };
 
@@ -98,11 +71,6 @@ template <>
 struct Fp8lElem<true> {
   static DEVINLINE unsigned pack(f32x2 f) {
     return AttnElem<true>::cvt_pk(f[0], f[1]);
-  }
-  static DEVINLINE f32x4 mfma(attn_u32x4 a, attn_u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(
-        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
-        c, 0, 0, 0);
   }
 };
 
@@ -190,7 +158,7 @@ DEVINLINE void fp8l_step(const unsigned char* const (&wrow)[NT],
             fp8l_cvt8<FP16>(wv[h][nt][2 * s], wv[h][nt][2 * s + 1]);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-          acc[nt][mt] = Fp8lElem<FP16>::mfma(a, xv[h][mt][s], acc[nt][mt]);
+          acc[nt][mt] = wq_mfma16<FP16>(a, xv[h][mt][s], acc[nt][mt]);
       }
     }
   }
@@ -463,44 +431,9 @@ void fp8_wide_kernel(const short* __restrict__ x,
 // repeatable and depend on (M, N, K, CU count) only. S depends on M, so unlike
 // the skinny kernel this path does NOT promise that a row's bits are
 // independent of the batch it sits in.
-constexpr int FP8G_BM = 128;      // x rows per workgroup
-constexpr int FP8G_BN = 128;      // channels per workgroup
-constexpr int FP8G_BK = 64;
-constexpr int FP8G_TILE_B = 128 * FP8G_BK * 2;     // one 16-bit image
+constexpr int FP8G_TILE_B = WQG_X_B;               // one 16-bit image
 constexpr int FP8G_STAGE_B = 2 * FP8G_TILE_B;      // x image, weight image
-constexpr int FP8G_MAX_SPLITS = 16;
-// BK steps a split keeps at least when S is chosen automatically: prologue,
-// epilogue and the partials' traffic are paid per split
-constexpr int FP8G_MIN_STEPS = 4;
-static_assert(FP8G_BM == FP8G_BN, "both images share fp8g_off");
-
-// byte offset of 16-byte chunk ch (0..7) of row `row` in an image
-DEVINLINE constexpr unsigned fp8g_off(int row, int ch) {
-  return (unsigned)(row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
-}
-
-template <bool FP16>
-DEVINLINE f32x16 fp8g_mfma(attn_u32x4 a, attn_u32x4 b, f32x16 c) {
-  if constexpr (FP16) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(
-        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
-        c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-        __builtin_bit_cast(fp8l_bf16x8, a), __builtin_bit_cast(fp8l_bf16x8, b),
-        c, 0, 0, 0);
-  }
-}
-
-// Wait for this wave's direct-to-LDS loads (counted on vmcnt; 0x0F70 is
-// vmcnt(0) alone), then a workgroup barrier with its LDS fences written out:
-// __syncthreads() is a call here, once per BK step.
-DEVINLINE void fp8g_publish() {
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+static_assert(WQG_BM == WQG_BA, "both images share wqg_xoff");
 
 // grid = (ceil(N/128), ceil(M/128), S); block = 256.
 // S == 1: writes y. S > 1: writes raw fp32 sums to part[S][M][N].
@@ -517,12 +450,12 @@ void fp8_gemm_kernel(const short* __restrict__ x,
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int wn = wave & 1, wm = wave >> 1;
   const int l31 = lane & 31, hi = lane >> 5;
-  const int n0 = blockIdx.x * FP8G_BN, m0 = blockIdx.y * FP8G_BM;
+  const int n0 = blockIdx.x * WQG_BA, m0 = blockIdx.y * WQG_BM;
   const int split = blockIdx.z, S = gridDim.z;
 
   // contiguous, balanced runs of BK steps over the splits; the host keeps
   // S <= T, so every split owns at least one step
-  const int T = (K + FP8G_BK - 1) / FP8G_BK, Tfull = K / FP8G_BK;
+  const int T = (K + WQG_BK - 1) / WQG_BK, Tfull = K / WQG_BK;
   const int t0 = (int)((long)split * T / S);
   const int t1 = (int)((long)(split + 1) * T / S);
 
@@ -543,12 +476,12 @@ void fp8_gemm_kernel(const short* __restrict__ x,
   for (int i = 0; i < 2; ++i) {
     const int row = i * 64 + (tid >> 2);
     wsrc[i] = w + (long)min(n0 + row, N - 1) * K + wq * 16;
-    wdst[i] = FP8G_TILE_B + fp8g_off(row, 2 * wq);
+    wdst[i] = FP8G_TILE_B + wqg_xoff(row, 2 * wq);
   }
 
   // issue the loads of step t: x into buffer `buf`, the codes into wv
   auto stage_load = [&](int t, int buf, attn_u32x4 (&wv)[2]) {
-    const int k0 = t * FP8G_BK;
+    const int k0 = t * WQG_BK;
     const bool tail = t >= Tfull;
     char* xi = lds + buf * FP8G_STAGE_B;
     if (!tail) {
@@ -594,7 +527,7 @@ void fp8_gemm_kernel(const short* __restrict__ x,
   attn_u32x4 wv[2];
   stage_load(t0, 0, wv);
   stage_commit(0, wv);
-  fp8g_publish();
+  wqg_publish<0>();
 
   // fragment reads: row 32*tile + l31 of the wave's half, chunk 2kk + hi
   const unsigned sw = (unsigned)((l31 >> 1) & 7);
@@ -608,7 +541,7 @@ void fp8_gemm_kernel(const short* __restrict__ x,
     if (more) stage_load(t + 1, cur ^ 1, wv);
     const char* base = lds + cur * FP8G_STAGE_B;
 #pragma unroll
-    for (int kk = 0; kk < FP8G_BK / 16; ++kk) {
+    for (int kk = 0; kk < WQG_BK / 16; ++kk) {
       const unsigned ch = (((unsigned)(2 * kk + hi)) ^ sw) << 4;
       attn_u32x4 a[2], b[2];
 #pragma unroll
@@ -622,11 +555,11 @@ void fp8_gemm_kernel(const short* __restrict__ x,
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[i][j] = fp8g_mfma<FP16>(a[i], b[j], acc[i][j]);
+          acc[i][j] = wq_mfma32<FP16>(a[i], b[j], acc[i][j]);
     }
     if (more) stage_commit(cur ^ 1, wv);
     // publishes buffer cur^1 and retires this step's reads of buffer cur
-    fp8g_publish();
+    wqg_publish<0>();
   }
 
   // lane: x row m of tile j; registers 4q..4q+3 of tile i: channels n..n+3
@@ -663,6 +596,79 @@ void fp8_gemm_kernel(const short* __restrict__ x,
 
 #pragma clang attribute pop
 
+namespace {
+
+// the per-format part of wq_operands: w8 [N,K] e4m3, scale [N] fp32
+struct Fp8Host {
+  static constexpr long K_MULT = 16;
+  static void check(const char* op, long K, const torch::Tensor& w8,
+                    const torch::Tensor& scale) {
+    TORCH_CHECK(scale.dim() == 1 &&
+                    w8.scalar_type() == torch::kFloat8_e4m3fn &&
+                    scale.scalar_type() == torch::kFloat,
+                op, ": w8 [N,K] float8_e4m3fn, scale [N] fp32");
+    TORCH_CHECK(w8.size(1) == K && scale.size(0) == w8.size(0),
+                op, ": shape mismatch");
+    TORCH_CHECK((uintptr_t)scale.data_ptr() % 16 == 0,
+                op, ": scale must be 16-byte aligned");
+  }
+};
+
+// Launch a skinny kernel: fp8_linear_kernel (split: S splits, any M) or the
+// (W, NT) instance of fp8_wide_kernel (M <= 64), PLAIN or SWIGLU by the
+// operands.
+torch::Tensor fp8_skinny(const torch::Tensor& x, const WqOperands& o, long W,
+                         long NT, bool split, long S) {
+  auto stream = at::hip::getCurrentHIPStream();
+  const long bn = o.swiglu ? 16 : 16 * NT;
+  const dim3 grid((unsigned)((o.N + bn - 1) / bn), (unsigned)S,
+                  (unsigned)(split ? (o.M + 63) / 64 : 1));
+  const dim3 block((unsigned)(W * WAVE));
+  const int mt = wq_skinny_mt(o.M);
+#define FP8W_LAUNCH(MTV, WV, NTV, SW)                                         \
+  hipLaunchKernelGGL((fp8_wide_kernel<kFP16, MTV, WV, NTV, SW>), grid, block, \
+                     0, stream, o.x, o.w[0], o.w[1], (const float*)o.s[0],    \
+                     (const float*)o.s[1], o.b[0], o.b[1], y, (int)o.M,       \
+                     (int)o.N, (int)o.K)
+#define FP8W_INSTANCE(MTV)                                  \
+  do {                                                      \
+    if (split) {                                            \
+      hipLaunchKernelGGL((fp8_linear_kernel<kFP16, MTV>), grid, block, 0,    \
+                         stream, o.x, o.w[0], (const float*)o.s[0], o.b[0],  \
+                         y, part, (int)o.M, (int)o.N, (int)o.K);             \
+    } else if (o.swiglu) {                                  \
+      if (W == 4) FP8W_LAUNCH(MTV, 4, 2, true);             \
+      else FP8W_LAUNCH(MTV, 8, 2, true);                    \
+    } else if (NT == 1) {                                   \
+      if (W == 4) FP8W_LAUNCH(MTV, 4, 1, false);            \
+      else FP8W_LAUNCH(MTV, 8, 1, false);                   \
+    } else {                                                \
+      if (W == 4) FP8W_LAUNCH(MTV, 4, 2, false);            \
+      else FP8W_LAUNCH(MTV, 8, 2, false);                   \
+    }                                                       \
+  } while (0)
+  return wq_run(
+      x, o, S,
+      [&](short* y, float* part) {
+        FP16_SWITCH(o.fp16, {
+          if (mt == 1) FP8W_INSTANCE(1);
+          else if (mt == 2) FP8W_INSTANCE(2);
+          else FP8W_INSTANCE(4);
+        });
+      },
+      [&](float* part, short* y, dim3 cgrid) {
+        FP16_SWITCH(o.fp16, {
+          hipLaunchKernelGGL((fp8_linear_combine_kernel<kFP16>), cgrid,
+                             dim3(256), 0, stream, part, (const float*)o.s[0],
+                             o.b[0], y, (int)o.M, (int)o.N, (int)S);
+        });
+      });
+#undef FP8W_INSTANCE
+#undef FP8W_LAUNCH
+}
+
+}  // namespace
+
 // Number of K splits across workgroups for an [N, K] weight on a device with
 // num_cus compute units. A function of (N, K, num_cus) only: the batch size
 // must not move a K boundary (batch invariance). Every wave slot keeps at
@@ -675,108 +681,31 @@ long fp8_linear_num_splits(long n, long k, long num_cus) {
   return std::max<long>(1, std::min(want, cap));
 }
 
-// y = (x @ dequant(w8)^T) * scale (+ bias). num_splits: 0 = chosen from
-// (N, K) and the CU count, otherwise forced (benchmarks, tests).
+// y = (x @ dequant(w8)^T) * scale (+ bias), any M >= 1. num_splits: 0 =
+// chosen from (N, K) and the CU count, otherwise forced (benchmarks, tests).
 torch::Tensor fp8_linear(torch::Tensor x, torch::Tensor w8,
                          torch::Tensor scale,
                          c10::optional<torch::Tensor> bias,
                          long num_splits) {
-  TORCH_CHECK(x.is_cuda() && w8.is_cuda() && scale.is_cuda(),
-              "fp8_linear: GPU tensors required");
-  TORCH_CHECK(x.dim() == 2 && w8.dim() == 2 && scale.dim() == 1,
-              "fp8_linear: x [M,K], w8 [N,K], scale [N]");
-  const bool fp16 = x.scalar_type() == torch::kHalf;
-  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
-              "fp8_linear: x must be bf16 or fp16");
-  TORCH_CHECK(w8.scalar_type() == torch::kFloat8_e4m3fn,
-              "fp8_linear: w8 must be float8_e4m3fn");
-  TORCH_CHECK(scale.scalar_type() == torch::kFloat,
-              "fp8_linear: scale must be fp32");
-  TORCH_CHECK(x.is_contiguous() && w8.is_contiguous() && scale.is_contiguous(),
-              "fp8_linear: contiguous operands");
-  TORCH_CHECK(w8.device() == x.device() && scale.device() == x.device(),
-              "fp8_linear: operands on different devices");
-  const long M = x.size(0), K = x.size(1), N = w8.size(0);
-  TORCH_CHECK(M >= 1 && N >= 1 && K >= 16 && K % 16 == 0,
-              "fp8_linear: K must be a positive multiple of 16");
-  TORCH_CHECK(w8.size(1) == K && scale.size(0) == N,
-              "fp8_linear: shape mismatch");
-  TORCH_CHECK(M * K < (1L << 31) && (M + 64) * N < (1L << 31),
-              "fp8_linear: problem too large");
-  const short* bias_p = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
-                    bias->scalar_type() == x.scalar_type() &&
-                    bias->dim() == 1 && bias->size(0) == N &&
-                    bias->is_contiguous(),
-                "fp8_linear: bias must be [N], contiguous, x's dtype/device");
-    bias_p = (const short*)bias->data_ptr();
-    TORCH_CHECK((uintptr_t)bias_p % 8 == 0, "fp8_linear: bias alignment");
-  }
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
-                  (uintptr_t)w8.data_ptr() % 16 == 0 &&
-                  (uintptr_t)scale.data_ptr() % 16 == 0,
-              "fp8_linear: operands must be 16-byte aligned");
-
+  const char* op = "fp8_linear";
+  const auto o = wq_operands<Fp8Host>(op, x, w8, scale, bias, nullptr, nullptr,
+                                      c10::nullopt);
+  wq_check_skinny_size(op, o, true);
   long S = num_splits;
   if (S <= 0) {
     S = fp8_linear_num_splits(
-        N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
+        o.N, o.K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
   }
-  const long steps = (K + FP8L_STEP - 1) / FP8L_STEP;
-  TORCH_CHECK(S <= FP8L_MAX_SPLITS, "fp8_linear: num_splits above ",
+  TORCH_CHECK(S <= FP8L_MAX_SPLITS, op, ": num_splits above ",
               FP8L_MAX_SPLITS);
-  S = std::max<long>(1, std::min(S, steps));
-
-  auto y = torch::empty({M, N}, x.options());
-  torch::Tensor part;
-  float* part_p = nullptr;
-  if (S > 1) {
-    part = torch::empty({S, M, N}, x.options().dtype(torch::kFloat));
-    part_p = part.data_ptr<float>();
-  }
-  auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid((N + FP8L_BN - 1) / FP8L_BN, S, (M + 63) / 64);
-  const dim3 block(FP8L_WAVES * WAVE);
-  const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
-#define FP8L_LAUNCH(MTV)                                                      \
-  hipLaunchKernelGGL((fp8_linear_kernel<kFP16, MTV>), grid, block, 0, stream, \
-                     (const short*)x.data_ptr(),                              \
-                     (const unsigned char*)w8.data_ptr(),                     \
-                     scale.data_ptr<float>(), bias_p, (short*)y.data_ptr(),   \
-                     part_p, (int)M, (int)N, (int)K)
-  FP16_SWITCH(fp16, {
-    if (mt == 1) FP8L_LAUNCH(1);
-    else if (mt == 2) FP8L_LAUNCH(2);
-    else FP8L_LAUNCH(4);
-  });
-#undef FP8L_LAUNCH
-  HIP_CHECK_LAST();
-  if (S > 1) {
-    const long groups = M * ((N + 3) / 4);
-    FP16_SWITCH(fp16, {
-      hipLaunchKernelGGL((fp8_linear_combine_kernel<kFP16>),
-                         dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
-                         stream, part_p, scale.data_ptr<float>(), bias_p,
-                         (short*)y.data_ptr(), (int)M, (int)N, (int)S);
-    });
-    HIP_CHECK_LAST();
-  }
-  return y;
+  S = std::max<long>(1, std::min(S, (o.K + FP8L_STEP - 1) / FP8L_STEP));
+  return fp8_skinny(x, o, FP8L_WAVES, FP8L_NT, true, S);
 }
 
 // Number of K splits of fp8_gemm for an [M, K] x [N, K]^T problem on a device
-// with num_cus compute units: 1 once the 128 x 128 tiles cover the CUs,
-// otherwise as many as bring the workgroup count up to the CU count, while
-// every split keeps at least FP8G_MIN_STEPS whole BK steps (one, where K has
-// fewer than that).
+// with num_cus compute units (wqg_splits on 128 x 128 tiles).
 long fp8_gemm_num_splits(long m, long n, long k, long num_cus) {
-  const long tiles =
-      ((m + FP8G_BM - 1) / FP8G_BM) * ((n + FP8G_BN - 1) / FP8G_BN);
-  const long steps = k / FP8G_BK;   // whole steps
-  const long want = num_cus / tiles;
-  const long cap = std::min<long>(FP8G_MAX_SPLITS, steps / FP8G_MIN_STEPS);
-  return std::max<long>(1, std::min(want, cap));
+  return wqg_splits(m, n, k, num_cus, WQG_BA);
 }
 
 // y = (x @ dequant(w8)^T) * scale (+ bias) for any M >= 1, on the tiled
@@ -784,86 +713,30 @@ long fp8_gemm_num_splits(long m, long n, long k, long num_cus) {
 // forced (benchmarks, tests).
 torch::Tensor fp8_gemm(torch::Tensor x, torch::Tensor w8, torch::Tensor scale,
                        c10::optional<torch::Tensor> bias, long num_splits) {
-  TORCH_CHECK(x.is_cuda() && w8.is_cuda() && scale.is_cuda(),
-              "fp8_gemm: GPU tensors required");
-  TORCH_CHECK(x.dim() == 2 && w8.dim() == 2 && scale.dim() == 1,
-              "fp8_gemm: x [M,K], w8 [N,K], scale [N]");
-  const bool fp16 = x.scalar_type() == torch::kHalf;
-  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
-              "fp8_gemm: x must be bf16 or fp16");
-  TORCH_CHECK(w8.scalar_type() == torch::kFloat8_e4m3fn,
-              "fp8_gemm: w8 must be float8_e4m3fn");
-  TORCH_CHECK(scale.scalar_type() == torch::kFloat,
-              "fp8_gemm: scale must be fp32");
-  TORCH_CHECK(x.is_contiguous() && w8.is_contiguous() && scale.is_contiguous(),
-              "fp8_gemm: contiguous operands");
-  TORCH_CHECK(w8.device() == x.device() && scale.device() == x.device(),
-              "fp8_gemm: operands on different devices");
-  const long M = x.size(0), K = x.size(1), N = w8.size(0);
-  TORCH_CHECK(M >= 1 && N >= 1 && K >= 16 && K % 16 == 0,
-              "fp8_gemm: K must be a positive multiple of 16");
-  TORCH_CHECK(w8.size(1) == K && scale.size(0) == N,
-              "fp8_gemm: shape mismatch");
-  TORCH_CHECK(M * K < (1L << 31) && (M + FP8G_BM) * N < (1L << 31) &&
-                  (M + FP8G_BM - 1) / FP8G_BM <= 65535,
-              "fp8_gemm: problem too large");
-  const short* bias_p = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
-                    bias->scalar_type() == x.scalar_type() &&
-                    bias->dim() == 1 && bias->size(0) == N &&
-                    bias->is_contiguous(),
-                "fp8_gemm: bias must be [N], contiguous, x's dtype/device");
-    bias_p = (const short*)bias->data_ptr();
-    TORCH_CHECK((uintptr_t)bias_p % 8 == 0, "fp8_gemm: bias alignment");
-  }
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
-                  (uintptr_t)w8.data_ptr() % 16 == 0 &&
-                  (uintptr_t)scale.data_ptr() % 16 == 0,
-              "fp8_gemm: operands must be 16-byte aligned");
-
-  long S = num_splits;
-  if (S <= 0) {
-    S = fp8_gemm_num_splits(
-        M, N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
-  }
-  TORCH_CHECK(S <= FP8G_MAX_SPLITS, "fp8_gemm: num_splits above ",
-              FP8G_MAX_SPLITS);
-  // every split keeps at least one whole BK step
-  S = std::max<long>(1, std::min(S, K / FP8G_BK));
-
-  auto y = torch::empty({M, N}, x.options());
-  torch::Tensor part;
-  float* part_p = nullptr;
-  if (S > 1) {
-    part = torch::empty({S, M, N}, x.options().dtype(torch::kFloat));
-    part_p = part.data_ptr<float>();
-  }
+  const char* op = "fp8_gemm";
+  const auto o = wq_operands<Fp8Host>(op, x, w8, scale, bias, nullptr, nullptr,
+                                      c10::nullopt);
+  const long S = wqg_check_splits(op, o, WQG_BA, num_splits);
   auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid((N + FP8G_BN - 1) / FP8G_BN, (M + FP8G_BM - 1) / FP8G_BM, S);
-  FP16_SWITCH(fp16, {
-    hipLaunchKernelGGL((fp8_gemm_kernel<kFP16>), grid, dim3(256), 0, stream,
-                       (const short*)x.data_ptr(),
-                       (const unsigned char*)w8.data_ptr(),
-                       scale.data_ptr<float>(), bias_p, (short*)y.data_ptr(),
-                       part_p, (int)M, (int)N, (int)K);
-  });
-  HIP_CHECK_LAST();
-  if (S > 1) {
-    const long groups = M * ((N + 3) / 4);
-    FP16_SWITCH(fp16, {
-      hipLaunchKernelGGL((fp8_linear_combine_kernel<kFP16>),
-                         dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
-                         stream, part_p, scale.data_ptr<float>(), bias_p,
-                         (short*)y.data_ptr(), (int)M, (int)N, (int)S);
-    });
-    HIP_CHECK_LAST();
-  }
-  return y;
+  const dim3 grid((unsigned)((o.N + WQG_BA - 1) / WQG_BA),
+                  (unsigned)((o.M + WQG_BM - 1) / WQG_BM), (unsigned)S);
+  return wq_run(
+      x, o, S,
+      [&](short* y, float* part) {
+        FP16_SWITCH(o.fp16, {
+          hipLaunchKernelGGL((fp8_gemm_kernel<kFP16>), grid, dim3(256), 0,
+                             stream, o.x, o.w[0], (const float*)o.s[0],
+                             o.b[0], y, part, (int)o.M, (int)o.N, (int)o.K);
+        });
+      },
+      [&](float* part, short* y, dim3 cgrid) {
+        FP16_SWITCH(o.fp16, {
+          hipLaunchKernelGGL((fp8_linear_combine_kernel<kFP16>), cgrid,
+                             dim3(256), 0, stream, part, (const float*)o.s[0],
+                             o.b[0], y, (int)o.M, (int)o.N, (int)S);
+        });
+      });
 }
-
-// ---------------------------------------------------------------------------
-// fp8_wide host side.
 
 // The (W, NT) instance of the one-launch kernel for an [N, K] weight (SWIGLU:
 // N = I, a gate/up pair) on a device with num_cus compute units. A function
@@ -888,104 +761,23 @@ std::vector<long> fp8_wide_instance(long n, long k, long num_cus,
 
 namespace {
 
-// one (weight, scale, bias) triple of a wide call against x [M, K]
-void fp8w_check(const char* op, const torch::Tensor& x,
-                const torch::Tensor& w8, const torch::Tensor& scale,
-                const c10::optional<torch::Tensor>& bias) {
-  TORCH_CHECK(w8.is_cuda() && scale.is_cuda() && w8.device() == x.device() &&
-                  scale.device() == x.device(),
-              op, ": weights and scales on x's GPU required");
-  TORCH_CHECK(w8.dim() == 2 && scale.dim() == 1 &&
-                  w8.scalar_type() == torch::kFloat8_e4m3fn &&
-                  scale.scalar_type() == torch::kFloat,
-              op, ": w8 [N,K] float8_e4m3fn, scale [N] fp32");
-  TORCH_CHECK(w8.is_contiguous() && scale.is_contiguous() &&
-                  w8.size(1) == x.size(1) && scale.size(0) == w8.size(0),
-              op, ": contiguous operands of matching shape");
-  TORCH_CHECK((uintptr_t)w8.data_ptr() % 16 == 0 &&
-                  (uintptr_t)scale.data_ptr() % 16 == 0,
-              op, ": operands must be 16-byte aligned");
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
-                    bias->scalar_type() == x.scalar_type() &&
-                    bias->dim() == 1 && bias->size(0) == w8.size(0) &&
-                    bias->is_contiguous() &&
-                    (uintptr_t)bias->data_ptr() % 8 == 0,
-                op, ": bias must be [N], contiguous, aligned, x's dtype");
-  }
-}
-
-// Shared front end: PLAIN when w1 is absent, SWIGLU otherwise.
-torch::Tensor fp8_wide(const char* op, torch::Tensor x, torch::Tensor w0,
-                       torch::Tensor s0, c10::optional<torch::Tensor> b0,
+// The one-launch front end: PLAIN when w1 is absent, SWIGLU otherwise.
+torch::Tensor fp8_wide(const char* op, const torch::Tensor& x,
+                       const torch::Tensor& w0, const torch::Tensor& s0,
+                       const c10::optional<torch::Tensor>& b0,
                        const torch::Tensor* w1, const torch::Tensor* s1,
-                       c10::optional<torch::Tensor> b1, long waves,
+                       const c10::optional<torch::Tensor>& b1, long waves,
                        long tiles) {
-  const bool swiglu = w1 != nullptr;
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
-                  (uintptr_t)x.data_ptr() % 16 == 0,
-              op, ": x must be a contiguous, aligned [M,K] GPU tensor");
-  const bool fp16 = x.scalar_type() == torch::kHalf;
-  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
-              op, ": x must be bf16 or fp16");
-  fp8w_check(op, x, w0, s0, b0);
-  if (swiglu) {
-    fp8w_check(op, x, *w1, *s1, b1);
-    TORCH_CHECK(w1->size(0) == w0.size(0), op, ": gate/up shape mismatch");
-  }
-  const long M = x.size(0), K = x.size(1), N = w0.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64, op, ": 1 <= M <= 64");
-  TORCH_CHECK(N >= 1 && K >= 16 && K % 16 == 0,
-              op, ": K must be a positive multiple of 16");
-  TORCH_CHECK(64 * K < (1L << 31) && 128 * N < (1L << 31),
-              op, ": problem too large");
-
+  const auto o = wq_operands<Fp8Host>(op, x, w0, s0, b0, w1, s1, b1);
+  wq_check_skinny_size(op, o, false);
   const auto inst = fp8_wide_instance(
-      N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
-      swiglu);
+      o.N, o.K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
+      o.swiglu);
   const long W = waves > 0 ? waves : inst[0];
-  const long NT = swiglu ? 2 : (tiles > 0 ? tiles : inst[1]);
+  const long NT = o.swiglu ? 2 : (tiles > 0 ? tiles : inst[1]);
   TORCH_CHECK((W == 4 || W == 8) && (NT == 1 || NT == 2),
               op, ": instances are waves in {4, 8}, tiles in {1, 2}");
-
-  auto y = torch::empty({M, N}, x.options());
-  auto stream = at::hip::getCurrentHIPStream();
-  const long bn = swiglu ? 16 : 16 * NT;
-  const dim3 grid((unsigned)((N + bn - 1) / bn)), block((unsigned)(W * WAVE));
-  const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
-  auto bp = [](const c10::optional<torch::Tensor>& b) {
-    return b.has_value() ? (const short*)b->data_ptr() : nullptr;
-  };
-#define FP8W_LAUNCH(MTV, WV, NTV, SW)                                        \
-  hipLaunchKernelGGL((fp8_wide_kernel<kFP16, MTV, WV, NTV, SW>), grid,       \
-                     block, 0, stream, (const short*)x.data_ptr(),           \
-                     (const unsigned char*)w0.data_ptr(),                    \
-                     SW ? (const unsigned char*)w1->data_ptr() : nullptr,    \
-                     s0.data_ptr<float>(),                                   \
-                     SW ? s1->data_ptr<float>() : nullptr, bp(b0), bp(b1),   \
-                     (short*)y.data_ptr(), (int)M, (int)N, (int)K)
-#define FP8W_INSTANCE(MTV)                                  \
-  do {                                                      \
-    if (swiglu) {                                           \
-      if (W == 4) FP8W_LAUNCH(MTV, 4, 2, true);             \
-      else FP8W_LAUNCH(MTV, 8, 2, true);                    \
-    } else if (NT == 1) {                                   \
-      if (W == 4) FP8W_LAUNCH(MTV, 4, 1, false);            \
-      else FP8W_LAUNCH(MTV, 8, 1, false);                   \
-    } else {                                                \
-      if (W == 4) FP8W_LAUNCH(MTV, 4, 2, false);            \
-      else FP8W_LAUNCH(MTV, 8, 2, false);                   \
-    }                                                       \
-  } while (0)
-  FP16_SWITCH(fp16, {
-    if (mt == 1) FP8W_INSTANCE(1);
-    else if (mt == 2) FP8W_INSTANCE(2);
-    else FP8W_INSTANCE(4);
-  });
-#undef FP8W_INSTANCE
-#undef FP8W_LAUNCH
-  HIP_CHECK_LAST();
-  return y;
+  return fp8_skinny(x, o, W, NT, false, 1);
 }
 
 }  // namespace

@@ -1,28 +1,26 @@
-// Weight-only MXFP4 linear layer for decode-sized batches (W4A16):
+// Weight-only MXFP4 linear layers (W4A16):
 //   y[M,N] = x[M,K] @ dequant(W4[N,K])^T (+ bias[N])
-// x, y bf16 or fp16, fp32 accumulation. The weight is in the OCP microscaling
-// format: e2m1 elements (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), two per byte (element
-// 2i in bits 0..3 of byte i, 2i+1 in bits 4..7), codes [N, K/2] row-major, and
-// one e8m0 scale byte per 32 elements along K, scales [N, K/32]: group g of row
-// n is multiplied by 2^(scales[n,g] - 127). A quarter of the 16-bit bytes and
-// half of the e4m3 ones that fp8_linear.hip streams.
+// The weight is in the OCP microscaling format: e2m1 elements
+// (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), two per byte (element 2i in bits 0..3 of
+// byte i, 2i+1 in bits 4..7), codes [N, K/2] row-major, and one e8m0 scale
+// byte per 32 elements along K, scales [N, K/32]: group g of row n is
+// multiplied by 2^(scales[n,g] - 127). A quarter of the 16-bit bytes and half
+// of the e4m3 ones that fp8_linear.hip streams. Operand order, kernel frames,
+// batch invariance and tail rules are in wq_gemm_common.h; this file holds the
+// format.
 //
-// Matrix instruction and operand order as in fp8_linear.hip:
-// v_mfma_f32_16x16x32_{bf16,f16} with the WEIGHTS as the A operand (lane l
-// holds channel l&15, k-slots 8*(l>>4)..+7), up to 16 activation rows as the B
-// operand, so the result is y^T: lane l owns activation row l&15 and channels
-// 4*(l>>4)..+3 of a tile, an 8-byte store along N.
-//
-// Weight stream: a lane's 16-byte load is 32 codes of its row, which is exactly
-// one scale group. The four lane groups of a row cover 64 contiguous bytes, and
-// a wave step issues the two loads of a 128-byte line back to back: 256 codes
-// per row and step. Dword s of the load feeds MFMA K-step s (4 per load)
-// through v_cvt_scalef32_pk_{bf16,f16}_fp4, one instruction per byte (two
-// elements) with the group's scale applied: 16 converts per load. The product
-// element * 2^e is exact in the 16-bit type (see the range note below), so the
-// conversion rounds nothing. The reduction order inside K is free, so the x
-// fragment follows the same permutation: lane (j, g) reads
-// x[j][k0 + 32g + 8s .. +7] for K-step s, 64 contiguous bytes per load.
+// Skinny weight stream (v_mfma_f32_16x16x32: lane l holds channel l&15,
+// k-slots 8*(l>>4)..+7): a lane's 16-byte load is 32 codes of its row, which
+// is exactly one scale group. The four lane groups of a row cover 64
+// contiguous bytes, and a wave step issues the two loads of a 128-byte line
+// back to back: 256 codes per row and step. Dword s of the load feeds MFMA
+// K-step s (4 per load) through v_cvt_scalef32_pk_{bf16,f16}_fp4, one
+// instruction per byte (two elements) with the group's scale applied: 16
+// converts per load. The product element * 2^e is exact in the 16-bit type
+// (see the range note below), so the conversion rounds nothing. The reduction
+// order inside K is free, so the x fragment follows the same permutation: lane
+// (j, g) reads x[j][k0 + 32g + 8s .. +7] for K-step s, 64 contiguous bytes per
+// load.
 //
 // Group scales: the 8 scale bytes of a row's step are contiguous
 // (scales[row][8t .. 8t+7]); a lane fetches them with one 8-byte load (rows
@@ -37,43 +35,22 @@
 // holds for exponents -14..12 (bytes 113..139) only; the fp16 contract is
 // limited to that range.
 //
-// One launch for every (N, K): K is cut only across the W in {4, 8} waves of a
-// workgroup, in contiguous, balanced runs of steps; the W accumulators are
-// summed through LDS in wave order after one barrier (the fp8_wide_kernel
-// pattern). No partials, no combine, no atomics: the result is bitwise
-// repeatable, and since W, NT and every K boundary come from (N, K, CU count)
-// alone, a row's bits depend neither on the batch it sits in nor on its
-// position.
+// mxfp4_linear / mxfp4_swiglu_linear: one launch for every (N, K), M <= 64; K
+// is cut only across the W in {4, 8} waves of a workgroup. Against the fp8
+// kernel the weight bytes per MFMA halve while the x bytes stay, so a wave
+// owns NT in {1, 2, 4} channel tiles per x fragment (an A fragment costs 4
+// VGPRs per 32 codes). The x fragments of one half (MT x 4 x 16 bytes) are
+// loaded per half, not per step, which keeps MT = 4 at 64 VGPRs of x. Built
+// instances (W, NT): (4,1) (8,1) (4,2) (8,2) (4,4); (8,4) would need 128 KiB
+// of reduction LDS at MT = 4 and is left out. The ragged step (K % 256 != 0,
+// whole 32-code groups) reads its scale bytes one by one, predicated.
 //
-// Tiles per wave: against the fp8 kernel the weight bytes per MFMA halve while
-// the x bytes stay, so a wave owns NT in {1, 2, 4} channel tiles per x
-// fragment (an A fragment costs 4 VGPRs per 32 codes). The x fragments of one
-// half (MT x 4 x 16 bytes) are loaded per half, not per step, which keeps
-// MT = 4 at 64 VGPRs of x. Built instances (W, NT): (4,1) (8,1) (4,2) (8,2)
-// (4,4); (8,4) would need 128 KiB of reduction LDS at MT = 4 and is left out.
-//
-// Epilogues: PLAIN y = acc (+ bias). SWIGLU: the wave's NT tiles are NT/2
-// tiles of the GATE weight and the same NT/2 tiles of the UP weight (two code
-// pointers, two scale pointers, nothing re-laid); one x fragment feeds both,
-// y = silu(g (+ bg)) * (u (+ bu)) in fp32; g and u never reach memory.
-//
-// Tails: channels >= N read a clamped row and are predicated at the store;
-// N % 4 != 0 takes scalar stores; rows >= M read row M-1 and are never stored;
-// the one ragged step at the end of K (K % 256 != 0, whole 32-code groups)
-// contributes zeros and reads its scale bytes one by one, predicated.
-//
-// mxfp4_dequantize further down writes the [N, K] 16-bit weight with the same
-// convert (16-byte loads and stores); it serves checkpoint export and the row
-// counts beyond the tiled mxfp4_gemm kernel (second half of this file), which
-// serves M > 64.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-#include <algorithm>
+// mxfp4_dequantize writes the [N, K] 16-bit weight with the same convert
+// (16-byte loads and stores); it serves checkpoint export. The tiled
+// mxfp4_gemm kernel (second half of this file) serves M > 64.
 #include <vector>
 
-#include "common.h"
-#include "attn_common.h"
+#include "wq_gemm_common.h"
 
 // packed fp32 VALU forms are kept out of this file's device code
 #pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), \
@@ -83,11 +60,7 @@ namespace {
 
 constexpr int MX4_STEP = 256;        // codes per wave step: one 128-byte line/row
 constexpr int MX4_GROUP = 32;        // codes per scale byte
-constexpr long MX4_MAX_M = 64;
 
-typedef __bf16 mx4_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mx4_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 mx4_f16x2 __attribute__((ext_vector_type(2)));
 // the 8 scale bytes of a row's step; rows start at any byte
 typedef unsigned mx4_u32x2_u __attribute__((ext_vector_type(2), aligned(1)));
 
@@ -121,19 +94,6 @@ DEVINLINE attn_u32x4 mx4_cvt8(unsigned c, float sc) {
         unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3));
   }
   return a;
-}
-
-template <bool FP16>
-DEVINLINE f32x4 mx4_mfma(attn_u32x4 a, attn_u32x4 b, f32x4 c) {
-  if constexpr (FP16) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(
-        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
-        c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-        __builtin_bit_cast(mx4_bf16x8, a), __builtin_bit_cast(mx4_bf16x8, b),
-        c, 0, 0, 0);
-  }
 }
 
 // One 256-code step t of a wave. Lane (j, g), half h: codes
@@ -199,121 +159,32 @@ DEVINLINE void mx4_step(const unsigned char* const (&wrow)[NT],
         const attn_u32x4 a = mx4_cvt8<FP16>(wv[h][nt][s], sc[h][nt]);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-          acc[nt][mt] = mx4_mfma<FP16>(a, xv[mt][s], acc[nt][mt]);
+          acc[nt][mt] = wq_mfma16<FP16>(a, xv[mt][s], acc[nt][mt]);
       }
     }
   }
 }
 
-// Bias, convert and store channels n..n+3 (n % 4 == 0) of row m. SWIGLU:
-// silu(v (+ b0)) * (u (+ b1)) in fp32.
-template <bool FP16, bool SWIGLU>
-DEVINLINE void mx4_finish4(f32x4 v, f32x4 u, long m, int n, int N,
-                           const short* __restrict__ b0,
-                           const short* __restrict__ b1,
-                           short* __restrict__ y) {
-  const bool vec = (N & 3) == 0;  // then n + 3 < N, 8-byte aligned row start
-  s16x4 ov;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int c = vec ? n + r : min(n + r, N - 1);
-    float o = v[r];
-    if (b0 != nullptr) o += AttnElem<FP16>::to_f32(b0[c]);
-    if constexpr (SWIGLU) {
-      float up = u[r];
-      if (b1 != nullptr) up += AttnElem<FP16>::to_f32(b1[c]);
-      // exp overflows to +inf for o < -88: the quotient is then -0, silu's
-      // limit
-      o = o / (1.f + __expf(-o)) * up;
+// wq_skinny_kernel's format: a code and a scale-row pointer per tile
+struct Mx4Fmt {
+  static constexpr int STEP = MX4_STEP;
+  template <int NT>
+  struct Rows {
+    const unsigned char* w[NT];
+    const unsigned char* s[NT];
+    DEVINLINE void set(int nt, const unsigned char* wp,
+                       const unsigned char* sp, long row, int K) {
+      w[nt] = wp + row * (K / 2);
+      s[nt] = sp + row * (K / MX4_GROUP);
     }
-    ov[r] = AttnElem<FP16>::from_f32(o);
+  };
+  template <bool FP16, int MT, bool TAIL, int NT>
+  static DEVINLINE void step(const Rows<NT>& rows,
+                             const short* const (&xrow)[MT], int t, int g,
+                             int K, f32x4 (&acc)[NT][MT]) {
+    mx4_step<FP16, MT, TAIL>(rows.w, rows.s, xrow, t, g, K, acc);
   }
-  if (vec) {
-    *reinterpret_cast<s16x4*>(y + m * N + n) = ov;
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (n + r < N) y[m * N + n + r] = ov[r];
-  }
-}
-
-// grid = ceil(N / BN), BN = 16 * NT (PLAIN) or 8 * NT (SWIGLU); block = W * 64.
-// PLAIN reads (w0, s0, b0) only. LDS: red[W][NT * MT][64] f32x4, at most 64 KiB.
-template <bool FP16, int MT, int W, int NT, bool SWIGLU>
-__global__ __launch_bounds__(W * WAVE)
-void mxfp4_linear_kernel(const short* __restrict__ x,
-                         const unsigned char* __restrict__ w0,
-                         const unsigned char* __restrict__ w1,
-                         const unsigned char* __restrict__ s0,
-                         const unsigned char* __restrict__ s1,
-                         const short* __restrict__ b0,
-                         const short* __restrict__ b1,
-                         short* __restrict__ y, int M, int N, int K) {
-  static_assert(!SWIGLU || NT % 2 == 0, "SWIGLU: as many gate as up tiles");
-  static_assert(W * NT * MT * WAVE * sizeof(f32x4) <= 64 * 1024, "LDS");
-  constexpr int CT = SWIGLU ? NT / 2 : NT;   // channel tiles per workgroup
-  constexpr int BN = 16 * CT;
-  __shared__ f32x4 red[W][NT * MT][WAVE];
-  const int tid = threadIdx.x, lane = tid % WAVE;
-  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
-  const int j = lane & 15, g = lane >> 4;
-  const int n0 = blockIdx.x * BN;
-
-  // contiguous, balanced runs of steps over the W waves
-  const int T = (K + MX4_STEP - 1) / MX4_STEP, Tfull = K / MX4_STEP;
-  const int t0 = (int)((long)wave * T / W);
-  const int t1 = (int)((long)(wave + 1) * T / W);
-
-  // tiles 0..CT-1 are w0's; SWIGLU: tiles CT..NT-1 are the same channels of w1.
-  // Rows past the end are clamped: loaded, multiplied, never stored.
-  const unsigned char* wrow[NT];
-  const unsigned char* srow[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const long row = min(n0 + (nt % CT) * 16 + j, N - 1);
-    wrow[nt] = (nt < CT ? w0 : w1) + row * (K / 2);
-    srow[nt] = (nt < CT ? s0 : s1) + row * (K / MX4_GROUP);
-  }
-  const short* xrow[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-    xrow[mt] = x + (long)min(mt * 16 + j, M - 1) * K;
-
-  f32x4 acc[NT][MT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int tm = min(t1, Tfull);
-  for (int t = t0; t < tm; ++t)
-    mx4_step<FP16, MT, false>(wrow, srow, xrow, t, g, K, acc);
-  if (t1 > Tfull)  // only the last wave, only when K % 256 != 0
-    mx4_step<FP16, MT, true>(wrow, srow, xrow, Tfull, g, K, acc);
-
-#pragma unroll
-  for (int i = 0; i < NT * MT; ++i) red[wave][i][lane] = acc[i / MT][i % MT];
-  __syncthreads();
-  // item (channel tile ct, column block mt, lane l) sums slot ct * MT + mt of
-  // waves 0..W-1 in that order; SWIGLU also the up slot (CT + ct) * MT + mt
-  constexpr int ITEMS = CT * MT * WAVE;
-  for (int idx = tid; idx < ITEMS; idx += W * WAVE) {
-    const int i = idx / WAVE, l = idx % WAVE;
-    const int m = (i % MT) * 16 + (l & 15);
-    const int n = n0 + (i / MT) * 16 + 4 * (l >> 4);
-    if (m >= M || n >= N) continue;
-    f32x4 v = red[0][i][l];
-#pragma unroll
-    for (int wv = 1; wv < W; ++wv) v += red[wv][i][l];
-    f32x4 u = v;
-    if constexpr (SWIGLU) {
-      u = red[0][CT * MT + i][l];
-#pragma unroll
-      for (int wv = 1; wv < W; ++wv) u += red[wv][CT * MT + i][l];
-    }
-    mx4_finish4<FP16, SWIGLU>(v, u, m, n, N, b0, b1, y);
-  }
-}
+};
 
 // A thread converts one scale group: 16 bytes of codes in, 64 bytes out.
 template <bool FP16>
@@ -332,25 +203,16 @@ void mxfp4_dequantize_kernel(const unsigned char* __restrict__ codes,
 }
 
 // ---------------------------------------------------------------------------
-// mxfp4_gemm: the same formula for M > 64 (prefill, mixed serving steps) as a
-// tiled GEMM that keeps the codes PACKED in LDS and converts them after the
-// fragment read.
-//
-// A workgroup of 4 waves computes 128 x rows by 128 weight (A) rows over
-// BK = 64 codes (two scale groups) per stage; the waves sit 2 (channels) x 2
-// (rows), each on 64 x 64 as 2 x 2 tiles of v_mfma_f32_32x32x16_{bf16,f16}.
-// The weights are the A operand, so the result is y^T: lane l owns x row l&31
-// of a tile and, per group of four accumulator registers q, the four
-// consecutive channels 8q + 4(l>>5)..+3: the epilogue is mx4_finish4.
+// mxfp4_gemm: the tiled kernel of wq_gemm_common.h with the codes kept PACKED
+// in LDS and converted after the fragment read. BK = 64 codes is two scale
+// groups per stage.
 //
 // LDS, per stage 20 KiB, MX4G_STAGES = 3 of them (60 KiB, two workgroups per
 // CU); both images are filled global -> LDS directly (attn_glds16, five per
 // thread and stage), with the swizzles on the source address:
-//   x      [128 rows][64 x 16 bit], 128-byte rows whose eight 16-byte chunks
-//          are XORed with (row>>1)&7 (fp8_gemm's image). The fragment of
-//          K-step s is chunk 4*hi + s of row l&31 (hi = l>>5): the reduction
-//          order inside a stage follows the weight side, as in the skinny
-//          kernel.
+//   x      the shared image. The fragment of K-step s is chunk 4*hi + s of
+//          row l&31 (hi = l>>5): the reduction order inside a stage follows
+//          the weight side, as in the skinny kernel.
 //   codes  [128 rows][32 bytes]: 256 slots of 16 bytes, one per thread; a
 //          slot is 32 codes, one scale group. Group `half` of row r sits in
 //          slot 2r + (half ^ ((r>>3)&1)). A lane's A fragment for the WHOLE
@@ -377,68 +239,23 @@ void mxfp4_dequantize_kernel(const unsigned char* __restrict__ codes,
 // silu(g (+ bg)) * (u (+ bu)) is formed in-lane in fp32, g and u never reach
 // memory and x is staged once for both. grid.x = ceil(I / 64).
 //
-// Tails: rows >= M read row M-1 and are never stored; channels >= N read row
-// N-1 and are predicated at the store. The one ragged step (K % 64 == 32) is
-// always the last: x goes through registers with chunks at or past K zeroed;
-// both code slots of a row are filled from its group 0 (no load leaves the
-// tensor), and lanes of half 1 zero their fragment and read scale 1.
-//
-// Split-K: where the tiles are fewer than the CUs, K is cut over grid.z into
-// contiguous, balanced runs of steps; fp32 partials [S][M][N] (SWIGLU:
-// [S][2][M][I]) are summed in split order by mxfp4_gemm_combine_kernel, which
-// applies the epilogue. No atomics: bits depend on (M, N, K, CU count) only.
-// S depends on M, so unlike the skinny kernel this path does NOT promise that
-// a row's bits are independent of the batch it sits in.
+// The ragged step (K % 64 == 32): both code slots of a row are filled from
+// its group 0 (no load leaves the tensor), and lanes of half 1 zero their
+// fragment and read scale 1.
 // -DMX4G_STAGES=2 builds the two-stage variant timed in
 // profiles/r20_mxfp4_gemm.md
 #ifndef MX4G_STAGES
 #define MX4G_STAGES 3
 #endif
-constexpr int MX4G_BM = 128;      // x rows per workgroup
-constexpr int MX4G_BA = 128;      // weight (A) rows per workgroup
-constexpr int MX4G_BK = 64;       // codes per stage
-constexpr int MX4G_X_B = MX4G_BM * MX4G_BK * 2;      // x image
-constexpr int MX4G_W_B = MX4G_BA * MX4G_BK / 2;      // packed code image
-constexpr int MX4G_STAGE_B = MX4G_X_B + MX4G_W_B;
+constexpr int MX4G_W_B = WQG_BA * WQG_BK / 2;      // packed code image
+constexpr int MX4G_STAGE_B = WQG_X_B + MX4G_W_B;
 constexpr int MX4G_LOADS = 5;     // direct loads per thread and full stage
-constexpr int MX4G_MAX_SPLITS = 16;
-// BK steps a split keeps at least when S is chosen automatically
-constexpr int MX4G_MIN_STEPS = 4;
 static_assert(MX4G_STAGES == 2 || MX4G_STAGES == 3, "two or three stages");
 static_assert(MX4G_STAGES * MX4G_STAGE_B <= 64 * 1024, "LDS");
 
-// byte offset of 16-byte chunk ch (0..7) of row `row` in the x image
-DEVINLINE constexpr unsigned mx4g_xoff(int row, int ch) {
-  return (unsigned)(row * 128 + ((ch ^ ((row >> 1) & 7)) << 4));
-}
 // byte offset of scale group `half` (0..1) of row `row` in the code image
 DEVINLINE constexpr unsigned mx4g_woff(int row, int half) {
   return (unsigned)((2 * row + (half ^ ((row >> 3) & 1))) << 4);
-}
-
-template <bool FP16>
-DEVINLINE f32x16 mx4g_mfma(attn_u32x4 a, attn_u32x4 b, f32x16 c) {
-  if constexpr (FP16) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(
-        __builtin_bit_cast(attn_f16x8, a), __builtin_bit_cast(attn_f16x8, b),
-        c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-        __builtin_bit_cast(mx4_bf16x8, a), __builtin_bit_cast(mx4_bf16x8, b),
-        c, 0, 0, 0);
-  }
-}
-
-// Wait until at most `PENDING` of this wave's loads are outstanding (vmcnt;
-// 0x0F70 waits for nothing else), then a workgroup barrier with its LDS
-// fences written out.
-template <int PENDING>
-DEVINLINE void mx4g_publish() {
-  static_assert(PENDING >= 0 && PENDING < 16, "vmcnt's low field");
-  __builtin_amdgcn_s_waitcnt(0x0F70 | PENDING);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // grid = (ceil(N / BN), ceil(M / 128), S), BN = 128 (PLAIN) or 64 (SWIGLU);
@@ -456,19 +273,19 @@ void mxfp4_gemm_kernel(const short* __restrict__ x,
                        short* __restrict__ y, float* __restrict__ part,
                        int M, int N, int K) {
   constexpr int NS = MX4G_STAGES;
-  constexpr int BN = SWIGLU ? MX4G_BA / 2 : MX4G_BA;
+  constexpr int BN = SWIGLU ? WQG_BA / 2 : WQG_BA;
   __shared__ __attribute__((aligned(16))) char lds[NS * MX4G_STAGE_B];
   const int tid = threadIdx.x, lane = tid % WAVE;
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int wn = wave & 1, wm = wave >> 1;
   const int l31 = lane & 31, hi = lane >> 5;
-  const int n0 = blockIdx.x * BN, m0 = blockIdx.y * MX4G_BM;
+  const int n0 = blockIdx.x * BN, m0 = blockIdx.y * WQG_BM;
   const int split = blockIdx.z, S = gridDim.z;
   const int G = K / MX4_GROUP;    // scale bytes per row
 
   // contiguous, balanced runs of BK steps over the splits; the host keeps
   // S <= max(1, K / BK), so every split owns at least one step
-  const int T = (K + MX4G_BK - 1) / MX4G_BK, Tfull = K / MX4G_BK;
+  const int T = (K + WQG_BK - 1) / WQG_BK, Tfull = K / WQG_BK;
   const int t0 = (int)((long)split * T / S);
   const int t1 = (int)((long)(split + 1) * T / S);
   // steps below tq have a full successor NS - 2 steps on
@@ -512,9 +329,9 @@ void mxfp4_gemm_kernel(const short* __restrict__ x,
   };
   // issue the loads of step t into buffer `buf`
   auto stage_load = [&](int t, int buf) {
-    const int k0 = t * MX4G_BK;
+    const int k0 = t * WQG_BK;
     char* xi = lds + buf * MX4G_STAGE_B;
-    char* wi = xi + MX4G_X_B + wave * WAVE * 16;
+    char* wi = xi + WQG_X_B + wave * WAVE * 16;
     if (t < Tfull) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -555,13 +372,13 @@ void mxfp4_gemm_kernel(const short* __restrict__ x,
   const unsigned sw = (unsigned)((l31 >> 1) & 7);
   const unsigned xrow_off = (unsigned)((wm * 64 + l31) * 128);
   const unsigned wslot_off =
-      (unsigned)MX4G_X_B + mx4g_woff(wn * 64 + l31, hi);
+      (unsigned)WQG_X_B + mx4g_woff(wn * 64 + l31, hi);
 
   int cur = 0;
   for (int t = t0; t < t1; ++t) {
     // publishes step t; retires the reads of step t-1's buffer
-    if (NS > 2 && t < tq) mx4g_publish<(NS - 2) * MX4G_LOADS>();
-    else mx4g_publish<0>();
+    if (NS > 2 && t < tq) wqg_publish<(NS - 2) * MX4G_LOADS>();
+    else wqg_publish<0>();
     if (t + 1 < t1) load_scales(t + 1, en);
     if (t + NS - 1 < t1) {
       const int nb = cur + NS - 1;
@@ -589,7 +406,7 @@ void mxfp4_gemm_kernel(const short* __restrict__ x,
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[i][j] = mx4g_mfma<FP16>(a[i], b[j], acc[i][j]);
+          acc[i][j] = wq_mfma32<FP16>(a[i], b[j], acc[i][j]);
     }
     sc[0] = mx4_scale(en[0]);
     sc[1] = mx4_scale(en[1]);
@@ -616,7 +433,7 @@ void mxfp4_gemm_kernel(const short* __restrict__ x,
                        acc[ti][j][4 * q + 2], acc[ti][j][4 * q + 3]};
         }
         if (S == 1) {
-          mx4_finish4<FP16, SWIGLU>(v[0], v[1], m, n, N, b0, b1, y);
+          wq_finish4<FP16, SWIGLU>(v[0], v[1], m, n, N, b0, b1, y);
           continue;
         }
 #pragma unroll
@@ -634,37 +451,6 @@ void mxfp4_gemm_kernel(const short* __restrict__ x,
       }
     }
   }
-}
-
-// y = epilogue(sum over splits, in split order); a thread per four channels
-// of one row. part is [S][M][N], SWIGLU [S][2][M][N].
-template <bool FP16, bool SWIGLU>
-__global__ __launch_bounds__(256)
-void mxfp4_gemm_combine_kernel(const float* __restrict__ part,
-                               const short* __restrict__ b0,
-                               const short* __restrict__ b1,
-                               short* __restrict__ y, int M, int N, int S) {
-  constexpr int P = SWIGLU ? 2 : 1;
-  const int n4 = (N + 3) / 4;
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)M * n4) return;
-  const long m = idx / n4;
-  const int n = (int)(idx % n4) * 4;
-  f32x4 v[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  for (int s = 0; s < S; ++s) {
-#pragma unroll
-    for (int h = 0; h < P; ++h) {
-      const float* p = part + (((long)s * P + h) * M + m) * N + n;
-      if ((N & 3) == 0) {
-        v[h] += *reinterpret_cast<const f32x4*>(p);
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (n + r < N) v[h][r] += p[r];
-      }
-    }
-  }
-  mx4_finish4<FP16, SWIGLU>(v[0], v[1], m, n, N, b0, b1, y);
 }
 
 }  // namespace
@@ -696,91 +482,52 @@ std::vector<long> mxfp4_linear_instance(long n, long k, long num_cus,
 
 namespace {
 
-// one (codes, scales, bias) triple of a call against x [M, K]
-void mx4_check(const char* op, const torch::Tensor& x,
-               const torch::Tensor& codes, const torch::Tensor& scales,
-               const c10::optional<torch::Tensor>& bias) {
-  TORCH_CHECK(codes.is_cuda() && scales.is_cuda() &&
-                  codes.device() == x.device() &&
-                  scales.device() == x.device(),
-              op, ": codes and scales on x's GPU required");
-  TORCH_CHECK(codes.dim() == 2 && scales.dim() == 2 &&
-                  codes.scalar_type() == torch::kByte &&
-                  scales.scalar_type() == torch::kByte,
-              op, ": codes [N,K/2] uint8, scales [N,K/32] uint8");
-  const long K = x.size(1);
-  TORCH_CHECK(codes.is_contiguous() && scales.is_contiguous() &&
-                  codes.size(1) * 2 == K && scales.size(1) * MX4_GROUP == K &&
-                  scales.size(0) == codes.size(0),
-              op, ": contiguous operands of matching shape");
-  TORCH_CHECK((uintptr_t)codes.data_ptr() % 16 == 0,
-              op, ": codes must be 16-byte aligned");
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
-                    bias->scalar_type() == x.scalar_type() &&
-                    bias->dim() == 1 && bias->size(0) == codes.size(0) &&
-                    bias->is_contiguous() &&
-                    (uintptr_t)bias->data_ptr() % 8 == 0,
-                op, ": bias must be [N], contiguous, aligned, x's dtype");
+// the per-format part of wq_operands: codes [N,K/2] and scales [N,K/32] uint8
+struct Mx4Host {
+  static constexpr long K_MULT = MX4_GROUP;
+  static void check(const char* op, long K, const torch::Tensor& codes,
+                    const torch::Tensor& scales) {
+    TORCH_CHECK(scales.dim() == 2 && codes.scalar_type() == torch::kByte &&
+                    scales.scalar_type() == torch::kByte,
+                op, ": codes [N,K/2] uint8, scales [N,K/32] uint8");
+    TORCH_CHECK(codes.size(1) * 2 == K && scales.size(1) * MX4_GROUP == K &&
+                    scales.size(0) == codes.size(0),
+                op, ": shape mismatch");
   }
-}
+};
 
-// Shared front end: PLAIN when c1 is absent, SWIGLU otherwise.
-torch::Tensor mx4_launch(const char* op, torch::Tensor x, torch::Tensor c0,
-                         torch::Tensor s0, c10::optional<torch::Tensor> b0,
+// The one-launch front end: PLAIN when c1 is absent, SWIGLU otherwise.
+torch::Tensor mx4_launch(const char* op, const torch::Tensor& x,
+                         const torch::Tensor& c0, const torch::Tensor& s0,
+                         const c10::optional<torch::Tensor>& b0,
                          const torch::Tensor* c1, const torch::Tensor* s1,
-                         c10::optional<torch::Tensor> b1, long waves,
+                         const c10::optional<torch::Tensor>& b1, long waves,
                          long tiles) {
-  const bool swiglu = c1 != nullptr;
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
-                  (uintptr_t)x.data_ptr() % 16 == 0,
-              op, ": x must be a contiguous, aligned [M,K] GPU tensor");
-  const bool fp16 = x.scalar_type() == torch::kHalf;
-  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
-              op, ": x must be bf16 or fp16");
-  const long M = x.size(0), K = x.size(1);
-  TORCH_CHECK(K >= MX4_GROUP && K % MX4_GROUP == 0,
-              op, ": K must be a positive multiple of 32");
-  mx4_check(op, x, c0, s0, b0);
-  if (swiglu) {
-    mx4_check(op, x, *c1, *s1, b1);
-    TORCH_CHECK(c1->size(0) == c0.size(0), op, ": gate/up shape mismatch");
-  }
-  const long N = c0.size(0);
-  TORCH_CHECK(M >= 1 && M <= MX4_MAX_M, op, ": 1 <= M <= 64");
-  TORCH_CHECK(N >= 1 && 64 * K < (1L << 31) && 128 * N < (1L << 31),
-              op, ": problem too large");
-
+  const auto o = wq_operands<Mx4Host>(op, x, c0, s0, b0, c1, s1, b1);
+  wq_check_skinny_size(op, o, false);
   const auto inst = mxfp4_linear_instance(
-      N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
-      swiglu);
+      o.N, o.K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
+      o.swiglu);
   const long W = waves > 0 ? waves : inst[0];
   const long NT = tiles > 0 ? tiles : inst[1];
   TORCH_CHECK((W == 4 || W == 8) && (NT == 1 || NT == 2 || NT == 4) &&
-                  !(W == 8 && NT == 4) && !(swiglu && NT == 1),
+                  !(W == 8 && NT == 4) && !(o.swiglu && NT == 1),
               op, ": instances are (waves, tiles) in (4,1) (8,1) (4,2) (8,2) "
                   "(4,4); SWIGLU counts gate and up tiles, so 2 or 4");
 
-  auto y = torch::empty({M, N}, x.options());
   auto stream = at::hip::getCurrentHIPStream();
-  const long bn = swiglu ? 8 * NT : 16 * NT;
-  const dim3 grid((unsigned)((N + bn - 1) / bn)), block((unsigned)(W * WAVE));
-  const int mt = M > 32 ? 4 : (M > 16 ? 2 : 1);
-  auto bp = [](const c10::optional<torch::Tensor>& b) {
-    return b.has_value() ? (const short*)b->data_ptr() : nullptr;
-  };
+  const long bn = o.swiglu ? 8 * NT : 16 * NT;
+  const dim3 grid((unsigned)((o.N + bn - 1) / bn)), block((unsigned)(W * WAVE));
+  const int mt = wq_skinny_mt(o.M);
 #define MX4_LAUNCH(MTV, WV, NTV, SW)                                          \
-  hipLaunchKernelGGL((mxfp4_linear_kernel<kFP16, MTV, WV, NTV, SW>), grid,    \
-                     block, 0, stream, (const short*)x.data_ptr(),            \
-                     (const unsigned char*)c0.data_ptr(),                     \
-                     SW ? (const unsigned char*)c1->data_ptr() : nullptr,     \
-                     (const unsigned char*)s0.data_ptr(),                     \
-                     SW ? (const unsigned char*)s1->data_ptr() : nullptr,     \
-                     bp(b0), bp(b1), (short*)y.data_ptr(), (int)M, (int)N,    \
-                     (int)K)
+  hipLaunchKernelGGL(                                                         \
+      (wq_skinny_kernel<Mx4Fmt, kFP16, MTV, WV, NTV, SW>), grid, block, 0,    \
+      stream, o.x, o.w[0], o.w[1], (const unsigned char*)o.s[0],              \
+      (const unsigned char*)o.s[1], o.b[0], o.b[1], y, (int)o.M, (int)o.N,    \
+      (int)o.K)
 #define MX4_INSTANCE(MTV)                                   \
   do {                                                      \
-    if (swiglu) {                                           \
+    if (o.swiglu) {                                         \
       if (NT == 4) MX4_LAUNCH(MTV, 4, 4, true);             \
       else if (W == 4) MX4_LAUNCH(MTV, 4, 2, true);         \
       else MX4_LAUNCH(MTV, 8, 2, true);                     \
@@ -794,15 +541,59 @@ torch::Tensor mx4_launch(const char* op, torch::Tensor x, torch::Tensor c0,
       else MX4_LAUNCH(MTV, 8, 1, false);                    \
     }                                                       \
   } while (0)
-  FP16_SWITCH(fp16, {
-    if (mt == 1) MX4_INSTANCE(1);
-    else if (mt == 2) MX4_INSTANCE(2);
-    else MX4_INSTANCE(4);
-  });
+  return wq_run(
+      x, o, 1,
+      [&](short* y, float*) {
+        FP16_SWITCH(o.fp16, {
+          if (mt == 1) MX4_INSTANCE(1);
+          else if (mt == 2) MX4_INSTANCE(2);
+          else MX4_INSTANCE(4);
+        });
+      },
+      [](float*, short*, dim3) {});
 #undef MX4_INSTANCE
 #undef MX4_LAUNCH
-  HIP_CHECK_LAST();
-  return y;
+}
+
+// The tiled front end: PLAIN when c1 is absent, SWIGLU otherwise.
+torch::Tensor mx4g_launch(const char* op, const torch::Tensor& x,
+                          const torch::Tensor& c0, const torch::Tensor& s0,
+                          const c10::optional<torch::Tensor>& b0,
+                          const torch::Tensor* c1, const torch::Tensor* s1,
+                          const c10::optional<torch::Tensor>& b1,
+                          long num_splits) {
+  const auto o = wq_operands<Mx4Host>(op, x, c0, s0, b0, c1, s1, b1);
+  const long bn = o.swiglu ? WQG_BA / 2 : WQG_BA;
+  const long S = wqg_check_splits(op, o, bn, num_splits);
+  auto stream = at::hip::getCurrentHIPStream();
+  const dim3 grid((unsigned)((o.N + bn - 1) / bn),
+                  (unsigned)((o.M + WQG_BM - 1) / WQG_BM), (unsigned)S);
+#define MX4G_LAUNCH(SW)                                                       \
+  hipLaunchKernelGGL((mxfp4_gemm_kernel<kFP16, SW>), grid, dim3(256), 0,      \
+                     stream, o.x, o.w[0], o.w[1],                             \
+                     (const unsigned char*)o.s[0],                            \
+                     (const unsigned char*)o.s[1], o.b[0], o.b[1], y, part,   \
+                     (int)o.M, (int)o.N, (int)o.K)
+#define MX4G_COMBINE(SW)                                                      \
+  hipLaunchKernelGGL((wq_combine_kernel<kFP16, SW>), cgrid, dim3(256), 0,     \
+                     stream, part, o.b[0], o.b[1], y, (int)o.M, (int)o.N,     \
+                     (int)S)
+  return wq_run(
+      x, o, S,
+      [&](short* y, float* part) {
+        FP16_SWITCH(o.fp16, {
+          if (o.swiglu) MX4G_LAUNCH(true);
+          else MX4G_LAUNCH(false);
+        });
+      },
+      [&](float* part, short* y, dim3 cgrid) {
+        FP16_SWITCH(o.fp16, {
+          if (o.swiglu) MX4G_COMBINE(true);
+          else MX4G_COMBINE(false);
+        });
+      });
+#undef MX4G_COMBINE
+#undef MX4G_LAUNCH
 }
 
 }  // namespace
@@ -869,110 +660,11 @@ torch::Tensor mxfp4_dequantize(torch::Tensor codes, torch::Tensor scales,
   return out;
 }
 
-// ---------------------------------------------------------------------------
-// mxfp4_gemm host side.
-
-namespace {
-
-// K splits for row tiles of 128 and channel tiles of bn: fp8_gemm_num_splits'
-// rule. 1 once the tiles cover the CUs, otherwise as many as bring the
-// workgroup count up to the CU count, while every split keeps at least
-// MX4G_MIN_STEPS whole BK steps.
-long mx4g_splits(long m, long n, long k, long num_cus, long bn) {
-  const long tiles = ((m + MX4G_BM - 1) / MX4G_BM) * ((n + bn - 1) / bn);
-  const long steps = k / MX4G_BK;   // whole steps
-  const long want = num_cus / tiles;
-  const long cap = std::min<long>(MX4G_MAX_SPLITS, steps / MX4G_MIN_STEPS);
-  return std::max<long>(1, std::min(want, cap));
-}
-
-// Shared front end: PLAIN when c1 is absent, SWIGLU otherwise.
-torch::Tensor mx4g_launch(const char* op, torch::Tensor x, torch::Tensor c0,
-                          torch::Tensor s0, c10::optional<torch::Tensor> b0,
-                          const torch::Tensor* c1, const torch::Tensor* s1,
-                          c10::optional<torch::Tensor> b1, long num_splits) {
-  const bool swiglu = c1 != nullptr;
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
-                  (uintptr_t)x.data_ptr() % 16 == 0,
-              op, ": x must be a contiguous, aligned [M,K] GPU tensor");
-  const bool fp16 = x.scalar_type() == torch::kHalf;
-  TORCH_CHECK(fp16 || x.scalar_type() == torch::kBFloat16,
-              op, ": x must be bf16 or fp16");
-  const long M = x.size(0), K = x.size(1);
-  TORCH_CHECK(K >= MX4_GROUP && K % MX4_GROUP == 0,
-              op, ": K must be a positive multiple of 32");
-  mx4_check(op, x, c0, s0, b0);
-  if (swiglu) {
-    mx4_check(op, x, *c1, *s1, b1);
-    TORCH_CHECK(c1->size(0) == c0.size(0), op, ": gate/up shape mismatch");
-  }
-  const long N = c0.size(0);
-  const long row_tiles = (M + MX4G_BM - 1) / MX4G_BM;
-  TORCH_CHECK(M >= 1 && N >= 1 && M * K < (1L << 31) &&
-                  (M + MX4G_BM) * N < (1L << 31) && row_tiles <= 65535,
-              op, ": problem too large");
-
-  const long bn = swiglu ? MX4G_BA / 2 : MX4G_BA;
-  long S = num_splits;
-  if (S <= 0) {
-    S = mx4g_splits(
-        M, N, K, at::cuda::getCurrentDeviceProperties()->multiProcessorCount,
-        bn);
-  }
-  TORCH_CHECK(S <= MX4G_MAX_SPLITS, op, ": num_splits above ",
-              MX4G_MAX_SPLITS);
-  // every split keeps at least one whole BK step
-  S = std::max<long>(1, std::min(S, K / MX4G_BK));
-
-  auto y = torch::empty({M, N}, x.options());
-  torch::Tensor part;
-  float* part_p = nullptr;
-  if (S > 1) {
-    part = torch::empty({S * (swiglu ? 2 : 1), M, N},
-                        x.options().dtype(torch::kFloat));
-    part_p = part.data_ptr<float>();
-  }
-  auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid((unsigned)((N + bn - 1) / bn), (unsigned)row_tiles,
-                  (unsigned)S);
-  const long groups = M * ((N + 3) / 4);
-  auto bp = [](const c10::optional<torch::Tensor>& b) {
-    return b.has_value() ? (const short*)b->data_ptr() : nullptr;
-  };
-#define MX4G_LAUNCH(SW)                                                       \
-  do {                                                                        \
-    hipLaunchKernelGGL((mxfp4_gemm_kernel<kFP16, SW>), grid, dim3(256), 0,    \
-                       stream, (const short*)x.data_ptr(),                    \
-                       (const unsigned char*)c0.data_ptr(),                   \
-                       SW ? (const unsigned char*)c1->data_ptr() : nullptr,   \
-                       (const unsigned char*)s0.data_ptr(),                   \
-                       SW ? (const unsigned char*)s1->data_ptr() : nullptr,   \
-                       bp(b0), bp(b1), (short*)y.data_ptr(), part_p, (int)M,  \
-                       (int)N, (int)K);                                       \
-    HIP_CHECK_LAST();                                                         \
-    if (S > 1) {                                                              \
-      hipLaunchKernelGGL((mxfp4_gemm_combine_kernel<kFP16, SW>),              \
-                         dim3((unsigned)((groups + 255) / 256)), dim3(256),   \
-                         0, stream, part_p, bp(b0), bp(b1),                   \
-                         (short*)y.data_ptr(), (int)M, (int)N, (int)S);       \
-      HIP_CHECK_LAST();                                                       \
-    }                                                                         \
-  } while (0)
-  FP16_SWITCH(fp16, {
-    if (swiglu) MX4G_LAUNCH(true);
-    else MX4G_LAUNCH(false);
-  });
-#undef MX4G_LAUNCH
-  return y;
-}
-
-}  // namespace
-
 // Number of K splits of mxfp4_gemm for an [M, K] x [N, K]^T problem on a
-// device with num_cus compute units (fp8_gemm_num_splits' rule on 128 x 128
-// tiles; mxfp4_swiglu_gemm applies it to its 128 x 64 tiles).
+// device with num_cus compute units (wqg_splits on 128 x 128 tiles;
+// mxfp4_swiglu_gemm applies it to its 128 x 64 tiles).
 long mxfp4_gemm_num_splits(long m, long n, long k, long num_cus) {
-  return mx4g_splits(m, n, k, num_cus, MX4G_BA);
+  return wqg_splits(m, n, k, num_cus, WQG_BA);
 }
 
 // y = x @ dequant(codes, scales)^T (+ bias) for any M >= 1, on the tiled

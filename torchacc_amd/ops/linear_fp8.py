@@ -139,10 +139,11 @@ def fp8_swiglu_linear(x: torch.Tensor, wg8: torch.Tensor, sg: torch.Tensor,
     return out.view(*shape[:-1], wg8.shape[0])
 
 
-def _keep_fp8_buffers(module: nn.Module, before) -> None:
+def _keep_buffer_dtypes(module: nn.Module, before) -> None:
     """After an ``_apply`` sweep: a dtype change (.to(bfloat16), .half()) is
-    meant for biases; codes and fp32 scales move device but keep their
-    types. ``before``: name -> buffer as it was."""
+    meant for biases; weight codes and scales (e4m3 and fp32 here, uint8 in
+    linear_mxfp4) move device but keep their types. ``before``: name ->
+    buffer as it was."""
     for name, old in before.items():
         new = getattr(module, name)
         if new.dtype != old.dtype:
@@ -172,7 +173,7 @@ class Fp8Linear(nn.Module):
     def _apply(self, fn, recurse=True):
         before = {n: getattr(self, n) for n in ("weight_fp8", "weight_scale")}
         super()._apply(fn, recurse)
-        _keep_fp8_buffers(self, before)
+        _keep_buffer_dtypes(self, before)
         return self
 
     def forward(self, x):
@@ -219,7 +220,7 @@ class Fp8SwiGLUMLP(nn.Module):
     def _apply(self, fn, recurse=True):
         before = {n: getattr(self, n) for n in self._FP8_BUFFERS}
         super()._apply(fn, recurse)
-        _keep_fp8_buffers(self, before)
+        _keep_buffer_dtypes(self, before)
         return self
 
     def forward(self, x):

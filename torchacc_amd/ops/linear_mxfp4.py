@@ -36,7 +36,7 @@ import torch.nn as nn
 
 from ._backend import dispatch
 from .linear import TunedLinear, tuned_linear
-from .linear_fp8 import _refuse_grad
+from .linear_fp8 import _keep_buffer_dtypes, _refuse_grad
 from .swiglu import swiglu
 
 MXFP4_GROUP = 32
@@ -207,16 +207,6 @@ def mxfp4_swiglu_linear(x: torch.Tensor, gate_codes: torch.Tensor,
     return out.view(*shape[:-1], gate_codes.shape[0])
 
 
-def _keep_uint8_buffers(module: nn.Module, before) -> None:
-    """After an ``_apply`` sweep: a dtype change (.to(float16), .float()) is
-    meant for biases; codes and scale bytes move device but stay uint8.
-    ``before``: name -> buffer as it was."""
-    for name, old in before.items():
-        new = getattr(module, name)
-        if new.dtype != old.dtype:
-            setattr(module, name, old.to(new.device))
-
-
 class Mxfp4Linear(nn.Module):
     """Linear layer holding MXFP4 weight codes and e8m0 group scales."""
 
@@ -239,7 +229,7 @@ class Mxfp4Linear(nn.Module):
         before = {n: getattr(self, n)
                   for n in ("weight_codes", "weight_scales")}
         super()._apply(fn, recurse)
-        _keep_uint8_buffers(self, before)
+        _keep_buffer_dtypes(self, before)
         return self
 
     def forward(self, x):
@@ -284,7 +274,7 @@ class Mxfp4SwiGLUMLP(nn.Module):
     def _apply(self, fn, recurse=True):
         before = {n: getattr(self, n) for n in self._UINT8_BUFFERS}
         super()._apply(fn, recurse)
-        _keep_uint8_buffers(self, before)
+        _keep_buffer_dtypes(self, before)
         return self
 
     def forward(self, x):
